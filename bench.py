@@ -25,6 +25,12 @@ Launch: `python bench.py --gpus N` with N > 1 spawns N rank processes itself
 (before anything touches the GPU), one per GPU; under torchrun WORLD_SIZE
 must equal --gpus.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the line.  `--full` adds the two CPU baselines (cpu_baseline,
+cpu_baseline_oracle: about --cpu-seconds each, after the timed region);
+`--dump-outputs DIR` writes the ensemble the last timed step left (pos, lnprob,
+naccept) as DIR/<name>.npy, identical from run to run for the same arguments.
+
 Kernel timing: the last warmup step records HIP events around every kernel
 (include/lfg.h LFG_NEV, on the caller stream all kernels run on) and picks
 the dominant kernel; in the timed region every --time-every-th ln_prob call
@@ -133,9 +139,14 @@ def parse(argv=None):
     ap.add_argument("--nsub", type=int, default=None)
     ap.add_argument("--shard-path", action="store_true",
                     help="run the multi-rank half-step (lfg_stretch_step_shard + accept_regen) on one rank")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="per CPU baseline (two are timed)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also time the two CPU baselines (a plain run sets up, warms up, "
+                         "times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the ensemble the last timed step left (pos, lnprob, naccept) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: per CPU baseline (two are timed)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every core this process may run on")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--exchange-path", action="store_true",
                     help="one GPU: a one-rank RCCL group and the multi-rank code path with its real "
                          "exchange (shard kernels, ncclAllGather on the compute stream, k_accept_regen)")
@@ -278,6 +289,18 @@ def line_value(W, steps, elapsed, emu=None):
     only those count."""
     evaluated = W // emu[1] if emu else W
     return evaluated * steps / elapsed
+
+
+def dump_outputs(S, path):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, one float64 .npy each: the walkers' positions [W, ndim], their
+    ln_prob [W] and their accepted-move counts since the starting ball [W].
+    The model, the data, the starting ball and the Philox stream are all
+    functions of the arguments (--seed), so two builds run with the same
+    arguments can be compared array for array."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("pos", S.pos), ("lnprob", S.lnp), ("naccept", S.naccept)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().cpu().numpy().astype(np.float64))
 
 
 def rank_block(dist, world, backend, own_ms, xch_ms, cnt, dev):
@@ -565,8 +588,11 @@ def run(args):
                      "counted_over_executed": dom_flops / f if f else None,
                      "source": pmc_path}
 
+    if args.dump_outputs and rank == 0:   # the ensemble is replicated on every rank
+        dump_outputs(S, args.dump_outputs)
+
     cpu = {"cpu_baseline": None}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(tree, S.pos.cpu().numpy(), args)
 
     if rank == 0:

@@ -46,6 +46,30 @@ def test_rank_block_two_gloo_ranks():
     np.testing.assert_allclose(b0["exchange_ms_per_half_step"], [0.01, 0.02])
 
 
+def test_plain_run_options_and_dump(tmp_path):
+    """a plain run times the steps only (--full adds the CPU baselines), and
+    --dump-outputs writes the ensemble as float64 .npy files"""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, None)
+    args = bench.parse(["--full", "--dump-outputs", str(tmp_path / "d")])
+    assert args.full and args.dump_outputs == str(tmp_path / "d")
+
+    class State:
+        pos = torch.arange(12, dtype=torch.float64).reshape(4, 3)
+        lnp = torch.tensor([-1.0, -2.0, float("-inf"), -4.0], dtype=torch.float64)
+        naccept = torch.tensor([0, 1, 2, 3], dtype=torch.int32)
+    bench.dump_outputs(State, args.dump_outputs)
+    assert sorted(os.listdir(args.dump_outputs)) == ["lnprob.npy", "naccept.npy", "pos.npy"]
+    for name, t in (("pos", State.pos), ("lnprob", State.lnp), ("naccept", State.naccept)):
+        got = np.load(os.path.join(args.dump_outputs, name + ".npy"))
+        assert got.dtype == np.float64
+        np.testing.assert_array_equal(got, t.numpy().astype(np.float64))
+
+
 def test_emulation_counts_evaluated_walkers():
     """--emulate-rank K/N holds the whole ensemble but evaluates W / N walkers
     per step: the line's value must count those"""

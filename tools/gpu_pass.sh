@@ -24,17 +24,17 @@ for s in $steps; do
   case $s in
     test)  args+=("${tag}_test:900:python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread") ;;
     smoke) args+=("${tag}_smoke:200:python3 -c 'import __graft_entry__ as g; g.smoke()'") ;;
-    c2)    args+=("${tag}_c2:300:python3 bench.py > $O/${tag}_c2.json") ;;
+    c2)    args+=("${tag}_c2:300:python3 bench.py --full > $O/${tag}_c2.json") ;;
     c2_20) args+=("${tag}_c2_20:200:python3 bench.py --steps 20 --warmup 5 --no-cpu > $O/${tag}_c2_20.json") ;;
     c2_20two) args+=("${tag}_c2_20two:200:LFG_PAIR=0 python3 bench.py --steps 20 --warmup 5 --no-cpu > $O/${tag}_c2_20_two.json") ;;
     p2)    args+=("${tag}_p2:200:rocprofv3 --kernel-trace --stats -d $O/${tag}_prof2 -o run --output-format csv -- python3 bench.py --steps 100 --warmup 5 --no-cpu") ;;
     pmc2)  args+=("${tag}_pmc2:900:bash tools/pmc_profile.sh ${tag}2") ;;
-    c3)    args+=("${tag}_c3:300:python3 bench.py --config 3 --steps 30 > $O/${tag}_c3.json") ;;
+    c3)    args+=("${tag}_c3:300:python3 bench.py --full --config 3 --steps 30 > $O/${tag}_c3.json") ;;
     c4)    args+=("${tag}_c4:300:python3 bench.py --config 4 --steps 20 --warmup 3 --no-cpu > $O/${tag}_c4.json") ;;
     c4e)   args+=("${tag}_c4e:300:python3 bench.py --config 4 --emulate-rank 0/8 --steps 20 --warmup 3 --no-cpu > $O/${tag}_c4_emu8.json") ;;
-    c5)    args+=("${tag}_c5:300:python3 bench.py --config 5 --steps 20 --warmup 3 > $O/${tag}_c5.json") ;;
-    gp)    args+=("${tag}_gp:300:python3 bench.py --config gp --steps 100 --warmup 5 > $O/${tag}_gp.json") ;;
-    gp_two) args+=("${tag}_gp_two:300:LFG_PAIR=0 python3 bench.py --config gp --steps 100 --warmup 5 > $O/${tag}_gp_two.json") ;;
+    c5)    args+=("${tag}_c5:300:python3 bench.py --full --config 5 --steps 20 --warmup 3 > $O/${tag}_c5.json") ;;
+    gp)    args+=("${tag}_gp:300:python3 bench.py --full --config gp --steps 100 --warmup 5 > $O/${tag}_gp.json") ;;
+    gp_two) args+=("${tag}_gp_two:300:LFG_PAIR=0 python3 bench.py --full --config gp --steps 100 --warmup 5 > $O/${tag}_gp_two.json") ;;
     c3_two) args+=("${tag}_c3_two:300:LFG_PAIR=0 python3 bench.py --config 3 --steps 30 --no-cpu > $O/${tag}_c3_two.json") ;;
     xch)   args+=("${tag}_xch:200:python3 bench.py --exchange-path --no-cpu > $O/${tag}_c2_xch.json") ;;
     p5)    args+=("${tag}_p5:300:rocprofv3 --kernel-trace --stats -d $O/${tag}_prof5 -o run --output-format csv -- python3 bench.py --config 5 --steps 6 --warmup 2 --no-cpu") ;;
