@@ -3442,6 +3442,10 @@ __device__ __forceinline__ bool sub_point_quiet(const SubTables& T, const SubEnt
         if (x < 0.1) {
             Dk = S * (sinc_small(x) / sinc_small(xs));
         } else {
+            // w >= 0.0159: reached at S = 1 only (Dk = 1).  With sub-bins a
+            // quiet window has no donor entry over 2 w (1 - 1 / S) >= w of
+            // phase, and the longest stretch without one is 0.0134 (edge-on;
+            // tests/test_long_windows.py surveys the prior's q and dphi)
             const double2 a = sincospi_ool(2.0 * wk), b = sincospi_ool(2.0 * h);
             Dk = a.x / b.x;
         }

@@ -1,0 +1,180 @@
+"""k_pair LONG's exposure windows by class, and the quiet window's closed form
+in numpy (no GPU).
+
+sub_point_quiet (lfit_python_amd/csrc/lfg.hip) sums a window's S sub-bins in
+closed form when nothing changes inside it, and hands every other window to
+the sub-bin loop.  classify() restates its conditions from the oracle's
+element tables (oracle.elements, oracle.findi), in the kernel's order of
+rejection:
+
+  zero        w <= 0 or NaN
+  wrap        the window [ph - w, ph + w], ph = wrap(x - phi0), leaves (-0.5, 0.5)
+  spot_edge   a spot element's ingress or egress lies in the window
+  beam_cross  a zero of the beaming term b lies in the window
+  donor       a donor tile's sign crossing lies between the first and the
+              last sub-bin centre, [ph - w + h, ph + w - h], h = w / S
+  quiet       none of these
+
+Every phase test is made twice, on the window shrunk and grown by MARGIN
+(>= the kernel's EPS = 1e-9).  A window is in a rejecting class when the
+shrunk test hits and quiet when no grown test does; one that only a grown
+test hits is `borderline` and in no other class.  The classes are exclusive.
+
+quiet splits by the spot's covering fraction E (the weight of the spot
+elements eclipsed over the whole window, over the strip's weight):
+quiet_offspot (E = 0), quiet_partial (0.02 < E < 0.98), quiet_full
+(E >= 0.98); and by the sign of b at the window's centre: quiet_lit (b > 0),
+quiet_dark (b <= 0).
+
+  b(theta) = sin t sin i cos(theta + psi) + cos t cos i,
+  psi = az - 90 deg + yaw                                   (MODEL_SPEC 5.3)
+  donor tile v crosses where v . e(theta) = 0,
+  e = (s cos theta, -s sin theta, c)                        (MODEL_SPEC 5.4)
+
+closed_form() is the quiet window's sum: with the sub-bin centres symmetric
+about ph and 2 h apart, sum_j (cos, sin)(theta_j) = D (cos, sin)(2 pi ph),
+D = sin(2 pi w) / sin(2 pi w / S) (the Dirichlet kernel).
+"""
+import numpy as np
+
+MARGIN = 1e-8
+NWD, NDISC, NBS = 400, 1000, 100
+TWO_PI = 2.0 * np.pi
+
+
+def _wrap(p):
+    return p - np.floor(p + 0.5)
+
+
+class Geometry:
+    """What the window tests need of one parameter set (14 or 18 values)."""
+
+    def __init__(self, oracle, pars):
+        pars = np.asarray(pars, dtype=np.float64)
+        st, a, b, wg, donor, geo = oracle.elements(pars)
+        if st:
+            raise ValueError("oracle.elements: status %d" % st)
+        self.pars = pars
+        inc = np.deg2rad(oracle.findi(pars[4], pars[5]))
+        self.s, self.c = np.sin(inc), np.cos(inc)
+        self.phi0 = pars[13]
+        self.fis = pars[11]
+        tilt, yaw = (pars[16], pars[17]) if pars.size == 18 else (90.0, 0.0)
+        t, self.psi = np.deg2rad(tilt), np.deg2rad(pars[10] - 90.0 + yaw)
+        self.bsin, self.bcos = np.sin(t) * self.s, np.cos(t) * self.c   # b = bsin cos(theta + psi) + bcos
+        self.bden, self.dnorm = geo[12], geo[13]
+        # the spot strip: the eclipsed elements' intervals and weights
+        sa, sb, sw = a[NWD + NDISC:], b[NWD + NDISC:], wg[NWD + NDISC:]
+        ecl = sa < sb
+        self.sa, self.sb, self.sw, self.bstot = sa[ecl], sb[ecl], sw[ecl], sw.sum()
+        self.spot_edges = np.sort(np.concatenate([self.sa, self.sb]))
+        self.donor = donor
+        # donor sign crossings: s rho cos(theta + alpha) + c v_z = 0
+        rho = self.s * np.hypot(donor[:, 0], donor[:, 1])
+        al = np.arctan2(donor[:, 1], donor[:, 0])
+        k = np.abs(self.c * donor[:, 2]) < rho
+        d = np.arccos(-self.c * donor[k, 2] / rho[k])
+        self.donor_cross = np.sort(_wrap(np.concatenate([-al[k] - d, -al[k] + d]) / TWO_PI))
+        # beaming zeros
+        self.beam_any = bool(abs(self.bsin) > abs(self.bcos))
+        if self.beam_any:
+            d = np.arccos(-self.bcos / self.bsin)
+            self.beam_zeros = np.sort(_wrap(np.array([-self.psi - d, -self.psi + d]) / TWO_PI))
+        else:
+            self.beam_zeros = np.empty(0)
+
+    def beam(self, ph):
+        return self.bsin * np.cos(TWO_PI * ph + self.psi) + self.bcos
+
+    def spot_cover(self, lo, hi):
+        """E: the weight of the spot elements eclipsed over all of [lo, hi]"""
+        cov = (self.sa[None, :] <= lo[:, None]) & (self.sb[None, :] >= hi[:, None])
+        return (cov * self.sw[None, :]).sum(1) / self.bstot
+
+
+def _any_in(sorted_pts, lo, hi):
+    """per window: does a point of sorted_pts lie in [lo, hi]"""
+    if sorted_pts.size == 0:
+        return np.zeros(lo.shape, bool)
+    return np.searchsorted(sorted_pts, hi, side="right") > np.searchsorted(sorted_pts, lo, side="left")
+
+
+def _hits(pts, lo, hi):
+    """(sure, maybe): a point in the window shrunk / grown by MARGIN"""
+    return _any_in(pts, lo + MARGIN, hi - MARGIN), _any_in(pts, lo - MARGIN, hi + MARGIN)
+
+
+def classify(oracle, pars, x, w, S, geom=None):
+    """dict of boolean masks over the points (see the module's docstring),
+    'beam_any' (bool), 'E' (the spot cover, valid on quiet windows) and
+    'geom'"""
+    g = geom or Geometry(oracle, pars)
+    x, w = np.asarray(x, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    n = x.size
+    zero = ~(w > 0.0)
+    wk = np.where(zero, 0.0, w)
+    ph = _wrap(x - g.phi0)
+    lo, hi, h = ph - wk, ph + wk, wk / S
+    live = ~zero
+    wrap_sure = live & ((lo < -0.5 - MARGIN) | (hi > 0.5 + MARGIN))
+    wrap_maybe = live & ~((lo > -0.5 + MARGIN) & (hi < 0.5 - MARGIN))
+    spot_sure, spot_maybe = _hits(g.spot_edges, lo, hi)
+    beam_sure, beam_maybe = _hits(g.beam_zeros, lo, hi)
+    don_sure, don_maybe = _hits(g.donor_cross, lo + h, hi - h)
+    out = {"zero": zero}
+    taken = zero.copy()
+    border = np.zeros(n, bool)
+    for name, sure, may in (("wrap", wrap_sure, wrap_maybe), ("spot_edge", spot_sure, spot_maybe),
+                            ("beam_cross", beam_sure, beam_maybe), ("donor", don_sure, don_maybe)):
+        # the kernel's order: the first test that hits takes the window, and
+        # one that only may hit leaves it borderline for good
+        undecided = ~taken & ~border
+        out[name] = undecided & sure
+        taken |= out[name]
+        border |= undecided & may & ~sure
+    quiet = ~taken & ~border
+    out["borderline"] = border
+    out["quiet"] = quiet
+    E = g.spot_cover(lo, hi)
+    out["E"] = E
+    out["quiet_offspot"] = quiet & (E == 0.0)
+    out["quiet_partial"] = quiet & (E > 0.02) & (E < 0.98)
+    out["quiet_full"] = quiet & (E >= 0.98)
+    bc = g.beam(ph)
+    out["quiet_lit"] = quiet & (bc > 0.0)
+    out["quiet_dark"] = quiet & ~(bc > 0.0)
+    out["beam_any"] = g.beam_any
+    out["geom"] = g
+    return out
+
+
+def closed_form(oracle, pars, x, w, S, geom=None):
+    """(ys, yrs): the bright spot's and the donor's flux of every point as a
+    quiet window's closed form gives them (oracle.flux's last two components
+    on quiet windows; meaningless on the others)"""
+    g = geom or Geometry(oracle, pars)
+    x, w = np.asarray(x, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    p = g.pars
+    sflux, rsflux = p[2], p[3]
+    wk = np.where(w > 0.0, w, 0.0)
+    ph = _wrap(x - g.phi0)
+    th = TWO_PI * ph
+    with np.errstate(invalid="ignore", divide="ignore"):
+        D = np.where(wk > 0.0, np.sin(TWO_PI * wk) / np.sin(TWO_PI * wk / S), float(S))
+    # donor: V the sum of the tiles counted at the centre (the same at every sub-bin of a quiet window)
+    e = np.stack([g.s * np.cos(th), -g.s * np.sin(th), np.full_like(th, g.c)], axis=1)
+    V = ((e @ g.donor.T) > 0.0).astype(np.float64) @ g.donor
+    yrs = rsflux * (g.s * D * (V[:, 0] * np.cos(th) - V[:, 1] * np.sin(th)) + S * g.c * V[:, 2]) / (g.dnorm * S)
+    # spot: (1 - E) [fis S + (1 - fis) sum_j b_j] / bden lit, (1 - E) fis S / bden dark
+    E = g.spot_cover(ph - wk, ph + wk)
+    lit = g.beam(ph) > 0.0
+    bsum = D * g.bsin * np.cos(th + g.psi) + S * g.bcos
+    B = g.fis * S + np.where(lit, (1.0 - g.fis) * bsum, 0.0)
+    ys = sflux * (1.0 - E) * B / (g.bden * S) if g.bden > 0.0 else np.zeros_like(th)
+    return ys, yrs
+
+
+def largest_donor_gap(geom):
+    """the longest stretch of phase with no donor sign crossing (cyclic)"""
+    c = geom.donor_cross
+    return float(np.max(np.diff(np.concatenate([c, c[:1] + 1.0]))))
