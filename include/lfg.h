@@ -388,6 +388,66 @@ int lfg_stretch_accept_dev(double* pos, double* lnp, int W, int ndim, int half,
                            void* stream);
 
 /*
+ * Parallel-tempered ensemble sampler (the role of ptemcee.Sampler in the
+ * reference's usePT = 1 path, mcmcfit.py:251-270): T temperature levels of W
+ * walkers each, every level an affine-invariant ensemble with fixed red/blue
+ * halves as above, plus swaps between adjacent levels.
+ *   pos   [dev] T x W x ndim     lnl, lnpr [dev] T x W  ln likelihood, ln prior
+ *   betas [dev] T inverse temperatures, betas[0] = 1, strictly decreasing
+ *         (0 allowed for the hottest); level t samples betas[t] lnl + lnpr
+ * One iteration is half 0, half 1, then lfg_pt_swap.  A half-step is
+ *   lfg_pt_propose -> q [T * W/2, ndim], zfac [T * W/2]   (proposal g =
+ *       t * W/2 + i is walker i of half `half` of level t; z, q and zfac as
+ *       lfg_stretch_propose forms them, the partner from the same level)
+ *   lfg_lnprob on the T * W/2 rows of q, with lnlike_e
+ *   lfg_pt_accept: lnl' = sum_e lnlike_e[g, e], lnpr' = lnp_new[g] - lnl',
+ *       accept iff ln u < zfac + betas[t] (lnl' - lnl) + (lnpr' - lnpr);
+ *       a lnp_new that is not finite (-inf, NaN) is rejected whatever
+ *       lnlike_e holds.  naccept [dev] T x W, nullable.
+ * lfg_pt_swap, for i = T - 1 down to 1 in order (pair i - 1 sees pair i's
+ * result): A and B are uniformly random permutations of the W slots of
+ * levels i and i - 1, each the stable argsort of W 32-bit keys; for every k
+ * slot (i, A[k]) and slot (i - 1, B[k]) exchange row, lnl and lnpr iff
+ *   ln u_k < (betas[i-1] - betas[i]) (lnl[i, A[k]] - lnl[i-1, B[k]]).
+ * lnl and lnpr are updated in place; the rows are gathered once, from pos_in
+ * into pos_out (another buffer: the caller ping-pongs), however many swaps
+ * chained through a slot.  T = 1: pos_out is a copy.  nswap [dev] T x 2
+ * uint64 counters, accumulated: [2 i] exchanges proposed, [2 i + 1] accepted
+ * between levels i and i - 1 (row 0 unused).  Three launches whatever T and
+ * W; none of these calls synchronises or copies to the host.
+ *
+ * Philox4x32-10 counters, key = seed, c.y / c.z = step lo / hi throughout:
+ *   c.w = half * 2 + 0, c.x = g   proposal: (x, y) -> u of z, z -> partner
+ *   c.w = half * 2 + 1, c.x = g   acceptance: (x, y) -> u
+ *       (for T = 1 these are the stretch move's own counters)
+ *   c.w = 4 + i, c.x = k          swap pair (i, i - 1): x = key of slot k in
+ *       A's sort, y = key of slot k in B's sort, (z, w) -> u_k
+ *
+ * Shape limits (LFG_E_ARGS beyond them): W even, 4 <= W <= LFG_PT_MAX_W (a
+ * level's permutation is sorted in LDS, 8 bytes per slot), T >= 1,
+ * T * W <= 2^30, ndim >= 1 (any: rows move with lanes across dimensions).
+ * ws: at least lfg_pt_workspace_size(T, W) bytes (0 for a refused shape),
+ * holding int perm[T - 1][2][W] (A then B of pair i at row i - 1; left there
+ * after the call for tests), the slot-origin map int org[T * W] and
+ * double lnu[T - 1][W] (ln u_k of pair i at row i - 1).
+ */
+#define LFG_PT_MAX_W 8192
+size_t lfg_pt_workspace_size(int T, int W);
+int lfg_pt_propose(const double* pos, int T, int W, int ndim, int half,
+                   double a, unsigned long long seed, unsigned long long step,
+                   double* q, double* zfac, void* stream);
+int lfg_pt_accept(double* pos, double* lnl, double* lnpr, int T, int W,
+                  int ndim, int half, const double* betas, const double* q,
+                  const double* zfac, const double* lnp_new,
+                  const double* lnlike_e, int E, unsigned long long seed,
+                  unsigned long long step, int* naccept, void* stream);
+int lfg_pt_swap(const double* pos_in, double* pos_out, double* lnl,
+                double* lnpr, int T, int W, int ndim, const double* betas,
+                unsigned long long seed, unsigned long long step,
+                unsigned long long* nswap, void* ws, size_t ws_bytes,
+                void* stream);
+
+/*
  * Batched trm.roche.wdphases(q, iangle, r1, ntheta) (CVModel.py:564): third
  * and fourth contact phases of a sphere of radius r1 at the white dwarf.
  * q, inc (degrees), r1, phi3, phi4, status: [dev] n.

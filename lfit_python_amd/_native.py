@@ -24,7 +24,8 @@ if os.environ.get("LFG_LIB"):
         raise RuntimeError("LFG_LIB=%s is set without LFG_DIAGNOSTIC=1: diagnostic builds are loaded only on "
                            "request (unset LFG_LIB to load %s)" % (os.environ["LFG_LIB"], LIB_PATH))
     LOAD_PATH = os.environ["LFG_LIB"]
-SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "lfg_components.hip")]
+SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "lfg_components.hip"),
+           os.path.join(_HERE, "csrc", "lfg_pt.hip")]  # lfg_pt.hip: the parallel-tempering kernels, a unit of their own
 # k_pair's fold and LONG instantiations: lfg.hip again, compiled on its own
 # without machine LICM (the reason: lfg.hip, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -32,6 +33,7 @@ SPLIT_FLAGS = ["-mllvm", "-disable-machine-licm"]
 HEADERS = [os.path.join(_HERE, "csrc", "lfg_device.hpp"),
            os.path.join(_HERE, "csrc", "lfg_tables.hpp"),
            os.path.join(_HERE, "csrc", "lfg_stream_table.h"),
+           os.path.join(_HERE, "csrc", "lfg_philox.hpp"),
            os.path.join(REPO, "include", "lfg.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
@@ -78,7 +80,8 @@ EXPORTS = ("lfg_workspace_size", "lfg_workspace_size_tree", "lfg_flux", "lfg_lnl
            "lfg_elements", "lfg_roche", "lfg_stretch_propose", "lfg_stretch_accept",
            "lfg_stretch_propose_dev", "lfg_stretch_accept_dev", "lfg_event_create", "lfg_event_destroy",
            "lfg_event_elapsed_ms", "lfg_wdphases", "lfg_gp_lnlike", "lfg_component_workspace_size",
-           "lfg_component", "lfg_version", "lfg_layout", "lfg_set_layout")
+           "lfg_component", "lfg_version", "lfg_layout", "lfg_set_layout",
+           "lfg_pt_workspace_size", "lfg_pt_propose", "lfg_pt_accept", "lfg_pt_swap")
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -228,6 +231,14 @@ def lib():
         L.lfg_stretch_propose_dev.argtypes = [vp, ip, ip, ip, f64, u64, vp, vp, vp, vp]
         L.lfg_stretch_accept_dev.restype = ip
         L.lfg_stretch_accept_dev.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, u64, vp, vp, vp]
+        L.lfg_pt_workspace_size.restype = sz
+        L.lfg_pt_workspace_size.argtypes = [ip, ip]
+        L.lfg_pt_propose.restype = ip
+        L.lfg_pt_propose.argtypes = [vp, ip, ip, ip, ip, f64, u64, u64, vp, vp, vp]
+        L.lfg_pt_accept.restype = ip
+        L.lfg_pt_accept.argtypes = [vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, ip, u64, u64, vp, vp]
+        L.lfg_pt_swap.restype = ip
+        L.lfg_pt_swap.argtypes = [vp, vp, vp, vp, ip, ip, ip, vp, u64, u64, vp, vp, sz, vp]
         L.lfg_event_create.restype = ip
         L.lfg_event_create.argtypes = [ctypes.POINTER(vp)]
         L.lfg_event_destroy.restype = ip

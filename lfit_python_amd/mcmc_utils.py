@@ -2,9 +2,12 @@
 device-resident EnsembleSampler: same names, arguments and file formats.
 
   initialise_walkers(p, scatter, nwalkers, ln_prior, model)   mcmc_utils.py:46-72
+  initialise_walkers_pt(p, scatter, nwalkers, ntemps, ln_prior, model)
+                                                                mcmc_utils.py:75-111
   run_burnin(sampler, startPos, nSteps, storechain=False)      mcmc_utils.py:114-132
   run_mcmc_save(sampler, startPos, nSteps, rState, file, col_names)
                                                                 mcmc_utils.py:135-183
+  run_ptmcmc_save(sampler, startPos, nSteps, file, col_names=)  mcmc_utils.py:186-239
   flatchain(chain, npars=None, nskip=0, thin=1)                 mcmc_utils.py:242-249
   readchain(file) / readchain_dask(file)                        mcmc_utils.py:252-300
   readflatchain(file)                                           mcmc_utils.py:303-306
@@ -30,6 +33,14 @@ def initialise_walkers(p, scatter, nwalkers, ln_prior, model=None, seed=0):
     else:
         fn = lambda x: np.array([ln_prior(v, model) for v in x])  # noqa: E731
     return _sampler.initialise_walkers(p, scatter, nwalkers, fn, seed=seed)
+
+
+def initialise_walkers_pt(p, scatter, nwalkers, ntemps, ln_prior, model=None, seed=0):
+    """A Gaussian ball per temperature level, all ntemps * nwalkers walkers
+    resampled together until every ln_prior is finite (mcmc_utils.py:75-111);
+    returns [ntemps, nwalkers, ndim].  ln_prior as in initialise_walkers."""
+    p0 = initialise_walkers(p, scatter, int(nwalkers) * int(ntemps), ln_prior, model, seed=seed)
+    return p0.reshape(int(ntemps), int(nwalkers), -1)
 
 
 def batched_ln_prior(evaluator):
@@ -79,6 +90,36 @@ def run_mcmc_save(sampler, startPos, nSteps, rState, file, col_names='', progres
         if writer:
             ch, lp = sampler.last_run()
             _sampler.write_chain(file, None, ch.cpu().numpy(), lp.cpu().numpy(), mode="a")
+        first = False
+        done += k
+    return sampler
+
+
+def run_ptmcmc_save(sampler, startPos, nSteps, file, col_names='', chunk=None):
+    """Parallel-tempered production run, the cold level written to `file`
+    (mcmc_utils.py:186-239): the header line col_names, then per step and
+    cold walker '{k:4d} {values} {ln_prob:f}' with the cold level's log
+    posterior (beta = 1: ln_like + ln_prior) as ln_prob.  startPos
+    [ntemps, nwalkers, ndim], or None to carry on from the sampler's state.
+    The steps run in bulk chunks (PTSampler.run_mcmc) instead of one file
+    open per row; the rows are the reference's format.  (The reference's
+    progress-bar switch is not taken: there is no bar.)"""
+    if startPos is None and not sampler.has_state:
+        raise ValueError("startPos is None and the sampler holds no state to carry on from")
+    if file:
+        with open(file, "w") as fh:
+            fh.write(col_names)
+            if col_names:
+                fh.write("\n")
+    W, ndim, T = sampler.W, sampler.ndim, (1 if sampler.cold_only else sampler.T)
+    chunk = chunk or max(1, min(nSteps, (1 << 28) // max(1, T * W * (ndim + 2) * 8)))
+    done, first = 0, True
+    while done < nSteps:
+        k = min(chunk, nSteps - done)
+        sampler.run_mcmc(startPos if first else None, k, storechain=True)
+        if file:
+            ch, lp, _ = sampler.last_run()
+            _sampler.write_chain(file, None, ch[:, 0].numpy(), lp[:, 0].numpy(), mode="a")
         first = False
         done += k
     return sampler

@@ -13,8 +13,12 @@ Same input file keys, checks and outputs as mcmcfit.py:51-343:
   double_burnin, re-centred on the best walker); reset; production written
   to chain_prod.txt in the reference's format (header
   'walker_no <names> ln_prob', one row per walker per step).
-Parallel tempering (usePT = 1, ptemcee) and the plots / e-mailed summary are
-out of scope; usePT = 1 is refused.
+With usePT = 1 the run is parallel-tempered over ntemps temperature levels
+(sampler.PTSampler in place of ptemcee, mcmcfit.py:251-270, 319-329): a
+walker ball per level, burn-in, with double_burnin a re-scatter of every
+level about the best cold walker, reset, and the cold level's chain written
+to chain_prod.txt with its log posterior as ln_prob.  One process only.
+The plots / e-mailed summary are out of scope.
 """
 import argparse
 import os
@@ -22,7 +26,7 @@ import sys
 
 import numpy as np
 
-from . import batch, cvmodel, sampler
+from . import batch, cvmodel, mcmc_utils, sampler
 
 
 def _cfg(cfg, key, conv, default=None):
@@ -96,9 +100,6 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
         return {"status": "prior_violation"}
     if not rc["fit"]:
         return {"status": "no_fit"}  # mcmcfit.py:181-182: report only
-    if rc["usePT"]:
-        raise NotImplementedError("parallel tempering (usePT = 1, ptemcee) is out of scope")
-
     names = model.dynasty_par_names
     npars = len(pars)
     nwalkers = rc["nwalkers"]
@@ -111,6 +112,8 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
         raise NameError("double_burnin needs comp_scat = 1 (the reference defines p0_scatter_2 only then)")
 
     tree = batch.compile_tree(model)
+    if rc["usePT"]:
+        return _run_pt(rc, tree, names, pars, s1, s2, dev, seed, chain_file, chunk, say)
     ev = batch.LnProbEvaluator(tree, device=dev, max_walkers=nwalkers)
     prior_fn = lambda p: ev.ln_prior(torch.as_tensor(p, device=dev)).cpu().numpy()
     S = sampler.EnsembleSampler(nwalkers, npars, ev, seed=seed)
@@ -146,8 +149,39 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
             "nprod": nprod}
 
 
+def _run_pt(rc, tree, names, pars, s1, s2, dev, seed, chain_file, chunk, say):
+    """The usePT = 1 branch of run() (mcmcfit.py:251-270, 290-329)."""
+    nwalkers, ntemps, npars = rc["nwalkers"], rc["ntemps"], len(pars)
+    say("MCMC using parallel tempering at {} levels, for {} total walkers.".format(ntemps, nwalkers * ntemps))
+    ev = batch.LnProbEvaluator(tree, device=dev, max_walkers=nwalkers * ntemps)
+    S = sampler.PTSampler(nwalkers, npars, ev, ntemps=ntemps, seed=seed, cold_only=True)
+    ln_prior = mcmc_utils.batched_ln_prior(ev)
+    p0 = mcmc_utils.initialise_walkers_pt(np.asarray(pars), s1, nwalkers, ntemps, ln_prior, seed=seed)
+
+    say("\n\nExecuting the burn-in phase...")
+    pos, prob, like = S.run_mcmc(p0, rc["nburn"], storechain=False)
+    if rc["double_burnin"]:
+        say("Executing the second burn-in phase")
+        best = pos[0][np.argmax(prob[0])]   # the cold level samples the posterior
+        p0 = mcmc_utils.initialise_walkers_pt(best, s2, nwalkers, ntemps, ln_prior, seed=seed + 1)
+        S.run_mcmc(p0, rc["nburn"], storechain=False)
+
+    S.reset()  # clears the counters; the state and the RNG stream carry on
+    say("Starting the main MCMC chain. Probably going to take a while!")
+    mcmc_utils.run_ptmcmc_save(S, None, rc["nprod"], chain_file,
+                               col_names="walker_no " + " ".join(names) + " ln_prob", chunk=chunk)
+    acc = S.acceptance_fraction.mean(axis=1)
+    tswap = S.tswap_acceptance_fraction
+    say("Mean acceptance fraction per level: " + " ".join("{:.3f}".format(x) for x in acc))
+    say("Swap acceptance fraction per level: " + " ".join("{:.3f}".format(x) for x in tswap))
+    return {"status": "ok", "chain_file": chain_file, "acceptance": float(acc[0]), "nwalkers": nwalkers,
+            "npars": npars, "nprod": rc["nprod"], "ntemps": ntemps, "betas": S.betas.tolist(),
+            "acceptance_levels": acc.tolist(), "tswap_acceptance": tswap.tolist()}
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="Execute an MCMC fit to a dataset (GPU ensemble).")
+    ap = argparse.ArgumentParser(description="Execute an MCMC fit to a dataset (GPU ensemble; usePT = 1 in the "
+                                             "input file runs it parallel-tempered over ntemps levels).")
     ap.add_argument("input", help="The filename for the MCMC parameters' input file.")
     ap.add_argument("--notify", default="", help="accepted for compatibility; e-mail is out of scope")
     ap.add_argument("--debug", action="store_true")

@@ -18,6 +18,7 @@ import os
 import numpy as np
 
 from . import _native
+from .pt import HipPTOps, PTSampler, default_betas  # noqa: F401  (the usePT = 1 sampler, pt.py)
 
 # comp_scat scatter factors (mcmcfit.py:208-232)
 SCATTER_FACTORS = {
