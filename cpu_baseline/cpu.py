@@ -107,6 +107,30 @@ class CpuPort:
             raise ValueError("lfg_cpu_lnlike: code %d" % rc)
         return out, st
 
+    def gp_predict(self, x, ye, obs, res, hyp, blocks, return_var=True, nthreads=0):
+        """lfg_cpu_gp_predict over a sorted merged grid: (mean [W, n],
+        var [W, n] or None, status [W])"""
+        x, ye = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (x, ye))
+        obs = np.ascontiguousarray(obs, dtype=np.int32).reshape(-1)
+        res = np.ascontiguousarray(np.atleast_2d(res), dtype=np.float64)
+        W, n = res.shape
+        hyp = np.ascontiguousarray(hyp, dtype=np.float64).reshape(W, 3)
+        blocks = np.ascontiguousarray(blocks, dtype=np.float64).reshape(W, -1, 2)
+        nb = blocks.shape[1]
+        mean = np.empty((W, n))
+        var = np.empty((W, n)) if return_var else None
+        st = np.empty(W, dtype=np.int32)
+        f = self.lib.lfg_cpu_gp_predict
+        f.restype = ctypes.c_int
+        f.argtypes = [_dp, _dp, _ip, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _ip,
+                      ctypes.c_int]
+        rc = f(x.ctypes.data_as(_dp), ye.ctypes.data_as(_dp), obs.ctypes.data_as(_ip), res.ctypes.data_as(_dp), W, n,
+               hyp.ctypes.data_as(_dp), blocks.ctypes.data_as(_dp) if nb else None, nb, mean.ctypes.data_as(_dp),
+               var.ctypes.data_as(_dp) if return_var else None, st.ctypes.data_as(_ip), int(nthreads))
+        if rc != 0:
+            raise ValueError("lfg_cpu_gp_predict: code %d" % rc)
+        return mean, var, st
+
     def lnprob(self, walkers, tree, nthreads=0):
         """lfg_cpu_lnprob through a struct lfg_tree of host arrays"""
         from lfit_python_amd import _native

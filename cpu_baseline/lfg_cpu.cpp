@@ -666,4 +666,56 @@ int lfg_cpu_lnprob(const double* walkers, int W, const lfg_tree* T, double* lnp,
     return LFG_OK;
 }
 
+// lfg_gp_predict's twin: GPForward and GPBackward (lfg_device.hpp, the text
+// the GPU compiles) over every vector, the records on the heap
+int lfg_cpu_gp_predict(const double* x, const double* ye, const int* obs, const double* res, int W, int n,
+                       const double* hyp, const double* blocks, int nb, double* mean, double* var, int* status,
+                       int nthreads)
+{
+    if (W <= 0 || n <= 0 || nb < 0 || !x || !ye || !obs || !res || !hyp || (nb > 0 && !blocks) || !mean || !status)
+        return LFG_E_ARGS;
+    if (nthreads <= 0) nthreads = omp_get_max_threads();
+#pragma omp parallel num_threads(nthreads)
+    {
+        std::vector<GPRecord> rec(n);
+        std::vector<int> blk(n);
+#pragma omp for schedule(static)
+        for (int w = 0; w < W; ++w) {
+            const double* bk = blocks + size_t(w) * nb * 2;
+            const double* r = res + size_t(w) * n;
+            GPForward F;
+            F.init(hyp[3 * w], hyp[3 * w + 1], hyp[3 * w + 2]);
+            for (int p = 0; p < n; ++p) {
+                int b = -1;
+                for (int k = 0; k < nb; ++k)
+                    if (x[p] >= bk[2 * k] && x[p] <= bk[2 * k + 1]) b = k;
+                blk[p] = b;
+                F.step(x[p], ye[p], r[p], b, obs[p] != 0, rec[p]);
+            }
+            status[w] = F.bad ? 1 : 0;
+            GPBackward<true> B;
+            GPBackward<false> Bm;
+            B.init();
+            Bm.init();
+            for (int p = n - 1; p >= 0; --p) {
+                double m, v = 0.0;
+                if (var)
+                    B.point(rec[p], blk[p] >= 0, obs[p] != 0, m, v);
+                else
+                    Bm.point(rec[p], blk[p] >= 0, obs[p] != 0, m, v);
+                mean[size_t(w) * n + p] = F.bad ? NAN : m;
+                if (var) var[size_t(w) * n + p] = F.bad ? NAN : v;
+                if (p > 0) {
+                    const bool fresh = blk[p] >= 0 && blk[p] != blk[p - 1];
+                    if (var)
+                        B.carry(F.lam, x[p] - x[p - 1], fresh);
+                    else
+                        Bm.carry(F.lam, x[p] - x[p - 1], fresh);
+                }
+            }
+        }
+    }
+    return LFG_OK;
+}
+
 }  // extern "C"

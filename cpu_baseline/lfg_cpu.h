@@ -32,6 +32,13 @@ int lfg_cpu_lnlike(const double* pars, int W, int P, const double* x,
 int lfg_cpu_lnprob(const double* walkers, int W, const lfg_tree* tree,
                    double* lnp, int nthreads);
 
+/* lfg_gp_predict's twin (gp.predict over a merged grid, MODEL_SPEC 10.5):
+ * mean, var [W][n] (var NULL: mean only), status [W]; any nb */
+int lfg_cpu_gp_predict(const double* x, const double* ye, const int* obs,
+                       const double* res, int W, int n, const double* hyp,
+                       const double* blocks, int nb, double* mean, double* var,
+                       int* status, int nthreads);
+
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */
 int lfc_lnprob_batch(const double* walkers, int W, int ndim, int E,

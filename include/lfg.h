@@ -473,6 +473,67 @@ int lfg_gp_lnlike(const double* x, const double* ye, const double* res, int W,
                   double* lnlike, void* stream);
 
 /*
+ * The same GP's posterior (george's gp.predict and gp.sample_conditional,
+ * plot_lc_model.py:229), exact and O(n) per vector: a Kalman filter and a
+ * modified Bryson-Frazier smoother over a merged grid (MODEL_SPEC 10.5).
+ *   x, ye   [dev] n, sorted by x: data and test points together
+ *   obs     [dev] n ints: 1 = a datum (res and ye are used), 0 = a test point
+ *           (the filter predicts there; res and ye are ignored)
+ *   res     [dev] W x n residuals
+ *   hyp     [dev] W x 3, blocks [dev] W x nb x 2 as for lfg_gp_lnlike;
+ *           nb <= LFG_GP_PREDICT_MAX_NB (the lanes' blocks are held in LDS)
+ *   mean    [dev] W x n conditional mean of the latent process at every point
+ *   var     [dev] W x n its variance (no ye^2), clamped at 0; NULL: mean only
+ *   status  [dev] W: non-zero, and NaN rows, for a descending x, a non-finite
+ *           residual at a datum, S <= 0 or an invalid hyper-parameter
+ *   ws      [dev] at least lfg_gp_predict_workspace_size(W, n) bytes: the
+ *           forward records, 7 doubles per point and vector
+ * lfg_gp_sample draws S conditional paths per vector by Matheron's rule:
+ * out [dev] W x S x n.  Its normals are Philox4x32-10, key = seed, counter
+ * (point, draw, first + vector, j), j = 0, 1: process noise of g and h,
+ * j = 2: the datum's noise; a draw depends on nothing else, so a batch cut
+ * into several calls (first = the index of each call's row 0) gives the same
+ * bits.  W * S <= 2^30.
+ * LFG_E_ARGS (and no launch) on null or short arguments, a refused shape, or
+ * ws_bytes below the size function's value.
+ */
+#define LFG_GP_PREDICT_MAX_NB 16
+size_t lfg_gp_predict_workspace_size(int W, int n);
+int lfg_gp_predict(const double* x, const double* ye, const int* obs,
+                   const double* res, int W, int n, const double* hyp,
+                   const double* blocks, int nb, double* mean, double* var,
+                   int* status, void* ws, size_t ws_bytes, void* stream);
+size_t lfg_gp_sample_workspace_size(int W, int n, int S);
+int lfg_gp_sample(const double* x, const double* ye, const int* obs,
+                  const double* res, int W, int n, const double* hyp,
+                  const double* blocks, int nb, int S, unsigned long long seed,
+                  int first, double* out, int* status, void* ws, size_t ws_bytes,
+                  void* stream);
+
+/*
+ * The GP posterior of every eclipse of a GP tree at its own data points, for
+ * W walkers: what plot_GP_eclipse draws, for a whole chain.  Runs lfg_lnprob's
+ * kernels (whichever layout is active), then the smoother over every
+ * (walker, eclipse) pair, with the pair's blocks and hyper-parameters as the
+ * likelihood used them (MODEL_SPEC 10.3's cache rule included).
+ *   flux, mean, var  [dev] W x off[E], the tree's concatenated point order:
+ *           the model flux y - res, the GP's conditional mean and variance;
+ *           flux and var may be NULL
+ *   status  [dev] W: 0, or the largest code over the walker's eclipses: an
+ *           LFG_ST_* model failure, 6 = ln_prior is -inf, 7 = no
+ *           changepoints, non-finite residuals or S <= 0.  Such a walker has
+ *           ln_prob = -inf as a whole; all its rows are NaN
+ *   ws      [dev] at least lfg_gp_predict_tree_workspace_size(W, tree) bytes
+ *           (lfg_workspace_size_tree's, W doubles and 8 doubles per point
+ *           and walker); lfg_workspace_size_tree itself is unchanged
+ * LFG_E_ARGS (and no launch) for a chi^2 tree, null arguments or a short ws.
+ */
+size_t lfg_gp_predict_tree_workspace_size(int W, const lfg_tree* tree);
+int lfg_gp_predict_tree(const double* walkers, int W, const lfg_tree* tree,
+                        double* flux, double* mean, double* var, int* status,
+                        void* ws, size_t ws_bytes, void* stream);
+
+/*
  * lfit's component objects (MODEL_SPEC 5.6): the unit-normalised flux of one
  * component for W parameter sets, at inclination inc (degrees, not dphi),
  * on a caller-chosen grid.  Replaces

@@ -25,7 +25,8 @@ if os.environ.get("LFG_LIB"):
                            "request (unset LFG_LIB to load %s)" % (os.environ["LFG_LIB"], LIB_PATH))
     LOAD_PATH = os.environ["LFG_LIB"]
 SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "lfg_components.hip"),
-           os.path.join(_HERE, "csrc", "lfg_pt.hip")]  # lfg_pt.hip: the parallel-tempering kernels, a unit of their own
+           os.path.join(_HERE, "csrc", "lfg_pt.hip"),  # lfg_pt.hip: the parallel-tempering kernels, a unit of their own
+           os.path.join(_HERE, "csrc", "lfg_gp_predict.hip")]  # the GP smoother and conditional sampler
 # k_pair's fold and LONG instantiations: lfg.hip again, compiled on its own
 # without machine LICM (the reason: lfg.hip, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -42,6 +43,7 @@ ARCH = "gfx950"
 NWD, NDISC, NBS, NDONOR = 400, 1000, 100, 400
 NEL = NWD + NDISC + NBS
 NGEO = 48
+GP_PREDICT_MAX_NB = 16  # LFG_GP_PREDICT_MAX_NB (include/lfg.h)
 
 STATUS_TEXT = {
     0: "ok",
@@ -81,7 +83,9 @@ EXPORTS = ("lfg_workspace_size", "lfg_workspace_size_tree", "lfg_flux", "lfg_lnl
            "lfg_stretch_propose_dev", "lfg_stretch_accept_dev", "lfg_event_create", "lfg_event_destroy",
            "lfg_event_elapsed_ms", "lfg_wdphases", "lfg_gp_lnlike", "lfg_component_workspace_size",
            "lfg_component", "lfg_version", "lfg_layout", "lfg_set_layout",
-           "lfg_pt_workspace_size", "lfg_pt_propose", "lfg_pt_accept", "lfg_pt_swap")
+           "lfg_pt_workspace_size", "lfg_pt_propose", "lfg_pt_accept", "lfg_pt_swap",
+           "lfg_gp_predict_workspace_size", "lfg_gp_predict", "lfg_gp_sample_workspace_size", "lfg_gp_sample",
+           "lfg_gp_predict_tree_workspace_size", "lfg_gp_predict_tree")
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -249,6 +253,18 @@ def lib():
         L.lfg_wdphases.argtypes = [vp, vp, vp, ip, ip, vp, vp, vp, vp]
         L.lfg_gp_lnlike.restype = ip
         L.lfg_gp_lnlike.argtypes = [vp, vp, vp, ip, ip, vp, vp, ip, vp, vp]
+        L.lfg_gp_predict_workspace_size.restype = sz
+        L.lfg_gp_predict_workspace_size.argtypes = [ip, ip]
+        L.lfg_gp_predict.restype = ip
+        L.lfg_gp_predict.argtypes = [vp, vp, vp, vp, ip, ip, vp, vp, ip, vp, vp, vp, vp, sz, vp]
+        L.lfg_gp_sample_workspace_size.restype = sz
+        L.lfg_gp_sample_workspace_size.argtypes = [ip, ip, ip]
+        L.lfg_gp_sample.restype = ip
+        L.lfg_gp_sample.argtypes = [vp, vp, vp, vp, ip, ip, vp, vp, ip, ip, u64, ip, vp, vp, vp, sz, vp]
+        L.lfg_gp_predict_tree_workspace_size.restype = sz
+        L.lfg_gp_predict_tree_workspace_size.argtypes = [ip, ctypes.POINTER(LfgTree)]
+        L.lfg_gp_predict_tree.restype = ip
+        L.lfg_gp_predict_tree.argtypes = [vp, ip, ctypes.POINTER(LfgTree), vp, vp, vp, vp, vp, sz, vp]
         L.lfg_component_workspace_size.restype = sz
         L.lfg_component_workspace_size.argtypes = [ip, ip, ip, ip]
         L.lfg_component.restype = ip

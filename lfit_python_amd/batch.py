@@ -378,6 +378,37 @@ class LnProbEvaluator:
         _native.check(rc, "lfg_lnprior")
         return out
 
+    def predict(self, walkers):
+        """The model flux and the GP's posterior at every data point, for
+        every walker [W, ndim] (lfg_gp_predict_tree): what the reference's
+        plot_GP_eclipse draws, for a batch of parameter sets.  Returns device
+        tensors {"flux", "gp_mean", "gp_var"} [W, off[E]] in the tree's point
+        order (tree.x: each eclipse sorted by phase, tree.order), "status" [W]
+        (non-zero: the priors or the model reject the walker, or its GP has no
+        posterior; its rows are NaN), and "off" = tree.offsets."""
+        import torch
+        if not self.tree.gp:
+            raise NotImplementedError("predict() serves GP trees (useGP = 1); the flux of a chi^2 tree comes from "
+                                      "lfit.CV")
+        if walkers.dtype != torch.float64 or walkers.device != self.device or not walkers.is_contiguous():
+            walkers = walkers.to(device=self.device, dtype=torch.float64).contiguous()
+        W, nd = walkers.shape
+        if nd != self.tree.ndim:
+            raise ValueError("walker vectors have %d entries, the tree has %d" % (nd, self.tree.ndim))
+        ntot = int(self.tree.offsets[-1])
+        nbytes = self.L.lfg_gp_predict_tree_workspace_size(W, ctypes.byref(self.ctree))
+        ws = _native.Workspace.get(nbytes, self.device)  # its own scratch: the sampler's workspace is left alone
+        out = {k: torch.empty((W, ntot), dtype=torch.float64, device=self.device)
+               for k in ("flux", "gp_mean", "gp_var")}
+        out["status"] = torch.empty(W, dtype=torch.int32, device=self.device)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = self.L.lfg_gp_predict_tree(vp(walkers), W, ctypes.byref(self.ctree), vp(out["flux"]), vp(out["gp_mean"]),
+                                        vp(out["gp_var"]), vp(out["status"]), vp(ws), nbytes,
+                                        _native.stream_ptr(self.device))
+        _native.check(rc, "lfg_gp_predict_tree")
+        out["off"] = self.tree.offsets
+        return out
+
 
 def ln_prob_batch(model, walkers, nsub=1):
     """Convenience: compile `model` and evaluate walkers [W, ndim] (numpy)."""

@@ -5977,6 +5977,23 @@ int lfg_gp_lnlike(const double* x, const double* ye, const double* res, int W, i
     return launch_ok();
 }
 
+// lfg_gp_predict.hip's window on what lfg_lnprob leaves in a GP tree's
+// workspace (carve()'s layout; not part of include/lfg.h): every pair's
+// record, status, residuals [pairs][max_n] and block indices, and the
+// walkers' ln_prior
+int lfg_tree_gp_views(void* wsp, int W, const lfg_tree* T, const double** geo, const int** status,
+                      const double** prior, const double** res, const int** gpb)
+{
+    if (!wsp || W <= 0 || !T || T->E <= 0 || !T->gp) return LFG_E_ARGS;
+    const Ws ws = carve(wsp, W, T->E, T->max_n);
+    *geo = ws.geo;
+    *status = ws.status;
+    *prior = ws.prior;
+    *res = ws.res;
+    *gpb = ws.gpb;
+    return LFG_OK;
+}
+
 #ifdef LFG_PROFILE_LIKE
 // diagnostic build only: k_lnlike prologue stamps
 int lfg_debug_like_cycles(unsigned long long* host)

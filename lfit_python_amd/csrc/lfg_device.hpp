@@ -1084,6 +1084,184 @@ struct GPFilter {
     }
 };
 
+// MODEL_SPEC 10.5: the GP's conditional mean and variance at every point of
+// a merged grid (data and test points together, sorted; obs = 0 marks a test
+// point: the filter predicts there and does not update).  The forward pass
+// is GPFilter's recursion and leaves one GPRecord per point; GPBackward is
+// the modified Bryson-Frazier smoother over those records, last point first
+// (tests/gp_smoother.py restates both in numpy).
+struct GPRecord {
+    double k0, k1, k2, k3;  // P_pred H
+    double S, v, yhat;      // innovation variance, innovation, H m_pred
+};
+
+struct GPForward : GPFilter {
+    __device__ void step(double x, double ye, double r, int blk, bool obs, GPRecord& o)
+    {
+        if (n > 0) {
+            const double d = x - xp;
+            const double u = lam * d, e = exp(-u);
+            const double f00 = e * (1.0 + u), f01 = e * d, f10 = -e * lam * u, f11 = e * (1.0 - u);
+            double t0 = f00 * m0 + f01 * m1;
+            m1 = f10 * m0 + f11 * m1;
+            m0 = t0;
+            t0 = f00 * m2 + f01 * m3;
+            m3 = f10 * m2 + f11 * m3;
+            m2 = t0;
+            sym(f00, f01, f10, f11, d00, d01, d11);
+            sym(f00, f01, f10, f11, d22, d23, d33);
+            const double t00 = f00 * d02 + f01 * d12, t01 = f00 * d03 + f01 * d13;
+            const double t10 = f10 * d02 + f11 * d12, t11 = f10 * d03 + f11 * d13;
+            d02 = t00 * f00 + t01 * f01;
+            d03 = t00 * f10 + t01 * f11;
+            d12 = t10 * f00 + t11 * f01;
+            d13 = t10 * f10 + t11 * f11;
+            bad = bad || !(d >= 0.0);
+        }
+        xp = x;
+        ++n;
+        if (blk >= 0 && blk != bp) {
+            m2 = m3 = 0.0;
+            d22 = d23 = d33 = d02 = d03 = d12 = d13 = 0.0;
+        }
+        bp = blk;
+        const double a = (blk >= 0) ? 1.0 : 0.0;
+        o.k0 = (d00 + ain) + a * d02;
+        o.k1 = d01 + a * d12;
+        o.k2 = d02 + a * (d22 + aout);
+        o.k3 = d03 + a * d23;
+        o.yhat = fma(a, m2, m0);
+        o.S = 1.0;
+        o.v = 0.0;
+        if (obs) {
+            const double S = fma(a, o.k2, o.k0) + ye * ye;
+            const double v = r - o.yhat;
+            const double iS = 1.0 / S;
+            bad = bad || !(S > 0.0) || !isfinite(v);
+            o.S = S;
+            o.v = v;
+            const double g = v * iS;
+            m0 = fma(o.k0, g, m0);
+            m1 = fma(o.k1, g, m1);
+            m2 = fma(o.k2, g, m2);
+            m3 = fma(o.k3, g, m3);
+            d00 -= o.k0 * o.k0 * iS; d01 -= o.k0 * o.k1 * iS; d11 -= o.k1 * o.k1 * iS;
+            d22 -= o.k2 * o.k2 * iS; d23 -= o.k2 * o.k3 * iS; d33 -= o.k3 * o.k3 * iS;
+            d02 -= o.k0 * o.k2 * iS; d03 -= o.k0 * o.k3 * iS; d12 -= o.k1 * o.k2 * iS; d13 -= o.k1 * o.k3 * iS;
+        }
+    }
+};
+
+// VAR = false carries no Lambda: the mean-only pass of sampling and of the
+// full covariance.  H = (1, 0, a, 0), a = 1 inside a block.
+template <bool VAR>
+struct GPBackward {
+    double l0, l1, l2, l3;                                   // lambda-hat
+    double L00, L01, L02, L03, L11, L12, L13, L22, L23, L33;  // Lambda-hat (symmetric)
+
+    __device__ void init()
+    {
+        l0 = l1 = l2 = l3 = 0.0;
+        L00 = L01 = L02 = L03 = L11 = L12 = L13 = L22 = L23 = L33 = 0.0;
+    }
+
+    // one point, given its record: the conditional mean and (VAR) variance
+    __device__ void point(const GPRecord& o, bool inblk, bool obs, double& mean, double& var)
+    {
+        const double a = inblk ? 1.0 : 0.0;
+        if (obs) {
+            const double iS = 1.0 / o.S;
+            // lambda~ = -H v / S + C^T lambda^, C = I - k H^T / S
+            const double c = (o.k0 * l0 + o.k1 * l1 + o.k2 * l2 + o.k3 * l3 + o.v) * iS;
+            l0 -= c;
+            l2 -= a * c;
+            if (VAR) {
+                // Lambda~ = H H^T / S + C^T Lambda^ C
+                //         = Lambda^ - (H w^T + w H^T) / S + H H^T (k^T w / S^2 + 1 / S),  w = Lambda^ k
+                const double w0 = L00 * o.k0 + L01 * o.k1 + L02 * o.k2 + L03 * o.k3;
+                const double w1 = L01 * o.k0 + L11 * o.k1 + L12 * o.k2 + L13 * o.k3;
+                const double w2 = L02 * o.k0 + L12 * o.k1 + L22 * o.k2 + L23 * o.k3;
+                const double w3 = L03 * o.k0 + L13 * o.k1 + L23 * o.k2 + L33 * o.k3;
+                const double q = ((o.k0 * w0 + o.k1 * w1 + o.k2 * w2 + o.k3 * w3) * iS + 1.0) * iS;
+                const double s0 = w0 * iS, s1 = w1 * iS, s2 = w2 * iS, s3 = w3 * iS;
+                L00 += q - 2.0 * s0;
+                L01 -= s1;
+                L02 += a * (q - s0) - s2;
+                L03 -= s3;
+                L12 -= a * s1;
+                L22 += a * (q - 2.0 * s2);
+                L23 -= a * s3;
+            }
+        }
+        mean = o.yhat - (o.k0 * l0 + o.k1 * l1 + o.k2 * l2 + o.k3 * l3);
+        if (VAR) {
+            const double w0 = L00 * o.k0 + L01 * o.k1 + L02 * o.k2 + L03 * o.k3;
+            const double w1 = L01 * o.k0 + L11 * o.k1 + L12 * o.k2 + L13 * o.k3;
+            const double w2 = L02 * o.k0 + L12 * o.k1 + L22 * o.k2 + L23 * o.k3;
+            const double w3 = L03 * o.k0 + L13 * o.k1 + L23 * o.k2 + L33 * o.k3;
+            var = fmax((o.k0 + a * o.k2) - (o.k0 * w0 + o.k1 * w1 + o.k2 * w2 + o.k3 * w3), 0.0);
+        }
+    }
+
+    // back through the transition of step d that led to this point:
+    // lambda^ <- F^T lambda~, Lambda^ <- F^T Lambda~ F, F = diag(Phi, Phi),
+    // its h rows zero where the point opened a block (fresh)
+    __device__ void carry(double lam, double d, bool fresh)
+    {
+        const double u = lam * d, e = exp(-u);
+        const double f00 = e * (1.0 + u), f01 = e * d, f10 = -e * lam * u, f11 = e * (1.0 - u);
+        const double z = fresh ? 0.0 : 1.0;
+        double t = f00 * l0 + f10 * l1;
+        l1 = f01 * l0 + f11 * l1;
+        l0 = t;
+        t = z * (f00 * l2 + f10 * l3);
+        l3 = z * (f01 * l2 + f11 * l3);
+        l2 = t;
+        if (VAR) {
+            // F^T = diag(Phi^T, Phi^T): sym() with Phi transposed
+            GPFilter::sym(f00, f10, f01, f11, L00, L01, L11);
+            GPFilter::sym(f00, f10, f01, f11, L22, L23, L33);
+            const double t00 = f00 * L02 + f10 * L12, t01 = f00 * L03 + f10 * L13;
+            const double t10 = f01 * L02 + f11 * L12, t11 = f01 * L03 + f11 * L13;
+            L02 = z * (t00 * f00 + t01 * f10);
+            L03 = z * (t00 * f01 + t01 * f11);
+            L12 = z * (t10 * f00 + t11 * f10);
+            L13 = z * (t10 * f01 + t11 * f11);
+            L22 *= z;
+            L23 *= z;
+            L33 *= z;
+        }
+    }
+};
+
+// MODEL_SPEC 10.5: Cholesky factor (c00, c10, c11) of Q / a, Q = Pinf - Phi
+// Pinf Phi^T the process noise of a step d, without cancellation: with
+// s = 2 lam d and T3 = sum_{k>=3} s^k / k!,
+//   Q00 = e^{-s} T3, Q01 = lam e^{-s} s^2 / 2, Q11 = lam^2 e^{-s} (2 s + T3);
+// the series below s = 1, the closed form above.  d = 0 gives exactly zero.
+__device__ inline void gp_step_noise(double lam, double d, double& c00, double& c10, double& c11)
+{
+    const double s = 2.0 * lam * d, e = exp(-s);
+    double q00, q11;
+    if (s < 1.0) {
+        double t3 = 0.0;
+        for (int k = 22; k >= 4; --k) t3 = (1.0 + t3) * s / k;
+        t3 = (1.0 + t3) * s * s * s / 6.0;
+        q00 = e * t3;
+        q11 = e * (2.0 * s + t3);
+    } else {
+        q00 = 1.0 - e * (1.0 + s + 0.5 * s * s);
+        q11 = 1.0 - e * (1.0 - s + 0.5 * s * s);
+    }
+    const double q01 = 0.5 * e * s * s;
+    c00 = c10 = c11 = 0.0;
+    if (q00 > 0.0) {
+        c00 = sqrt(q00);
+        c10 = lam * q01 / c00;
+        c11 = lam * sqrt(fmax(q11 - q01 * q01 / q00, 0.0));
+    }
+}
+
 // CVModel.py:582-599: changepoint block k of eclipse number ec is
 // [(ec - 1) + dcp + phi0, (ec - dcp) + phi0], closed as george tests blocks;
 // returns the block index of x in [e0, e1], or -1

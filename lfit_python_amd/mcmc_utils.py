@@ -11,6 +11,8 @@ device-resident EnsembleSampler: same names, arguments and file formats.
   flatchain(chain, npars=None, nskip=0, thin=1)                 mcmc_utils.py:242-249
   readchain(file) / readchain_dask(file)                        mcmc_utils.py:252-300
   readflatchain(file)                                           mcmc_utils.py:303-306
+  posterior_predictive(ev, samples, chunk=)   the numbers behind
+                                              plot_lc_model.plot_GP_eclipse
 
 The emcee RNG state the reference threads from the burn-in into production
 (`state` -> `rstate0`) is the sampler's Philox counter here
@@ -134,6 +136,35 @@ def flatchain(chain, npars=None, nskip=0, thin=1):
     if npars is None:
         npars = chain.shape[2]
     return chain[:, nskip::thin, :].reshape((-1, npars))
+
+
+def posterior_predictive(ev, samples, chunk=1024):
+    """Per data point, over the flat chain samples [n, ndim], the 16 / 50 /
+    84 percentiles of the model flux and of flux + GP mean, and the mean GP
+    standard deviation: the bands of the reference's plot_GP_eclipse
+    (plot_lc_model.py:208-265) from the whole posterior instead of one
+    parameter set.  ev is a batch.LnProbEvaluator of a GP tree; the samples go
+    through ev.predict `chunk` at a time.  Samples the priors or the model
+    reject (status != 0) are left out.  Returns numpy arrays in the tree's
+    point order: {"x", "off", "flux" [3, N], "flux_gp" [3, N], "gp_std" [N],
+    "used": the number of samples kept}."""
+    import torch
+    if hasattr(samples, "cpu"):
+        samples = samples.cpu().numpy()
+    samples = np.ascontiguousarray(np.asarray(samples, dtype=np.float64).reshape(-1, ev.tree.ndim))
+    flux, mean, std = [], [], []
+    for lo in range(0, len(samples), int(chunk)):
+        r = ev.predict(torch.as_tensor(samples[lo:lo + int(chunk)], device=ev.device))
+        ok = (r["status"] == 0).cpu().numpy()
+        flux.append(r["flux"].cpu().numpy()[ok])
+        mean.append(r["gp_mean"].cpu().numpy()[ok])
+        std.append(np.sqrt(r["gp_var"].cpu().numpy()[ok]))
+    flux, mean, std = (np.concatenate(a) for a in (flux, mean, std))
+    if not len(flux):
+        raise ValueError("no sample has a posterior: every status is non-zero")
+    q = (16.0, 50.0, 84.0)
+    return {"x": ev.tree.x, "off": ev.tree.offsets, "flux": np.percentile(flux, q, axis=0),
+            "flux_gp": np.percentile(flux + mean, q, axis=0), "gp_std": std.mean(axis=0), "used": len(flux)}
 
 
 def readchain(file, **kwargs):
