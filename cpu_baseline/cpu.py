@@ -2,7 +2,7 @@
 CPU baseline for bench.py, beside the oracle.  Not a product path: nothing
 in lfit_python_amd loads it.
 
-    build(out=None, march="native") -> path of liblfg_cpu.so
+    build(out=None, march="x86-64-v3", extra=()) -> path of liblfg_cpu.so
     CpuPort(path).lnprob_batch(walkers, tree, nthreads=0) -> (lnp, threads)
 """
 import ctypes
@@ -18,9 +18,10 @@ _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
 
 
-def build(out=None, march="x86-64-v3"):
+def build(out=None, march="x86-64-v3", extra=()):
+    """extra: further compiler flags (diagnostic builds: -DLFC_COUNT, -DLFG_F32_OPEN=0)"""
     out = out or LIB_PATH
-    cmd = ["g++", "-O3", "-march=%s" % march, "-fopenmp", "-std=c++17", "-fPIC", "-shared",
+    cmd = ["g++", "-O3", "-march=%s" % march, "-fopenmp", "-std=c++17", "-fPIC", "-shared"] + list(extra) + [
            "-I", HERE, "-I", os.path.join(HERE, "shim"), "-I", os.path.join(ROOT, "lfit_python_amd", "csrc"),
            "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp")]
     subprocess.run(cmd, check=True)

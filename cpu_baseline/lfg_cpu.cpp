@@ -165,14 +165,21 @@ static void count_pair(const int* cost, int n)
 #pragma omp atomic
     g_cnt[3] += cm;
 }
+// lfc_counts2: FP32 opener lane steps, nested-solver fallbacks, donor tiles, their FP64 root steps, their FP32 root steps
+static unsigned long long g_cnt2[5];
+extern "C" void lfc_counts2(unsigned long long* o) { for (int i = 0; i < 5; ++i) o[i] = g_cnt2[i]; }
+static void count2(int i, unsigned long long v)
+{
+#pragma omp atomic
+    g_cnt2[i] += v;
+}
 #define LFC_NIT int nit[3] = {0, 0, 0}; bool fb = false; double gs[2] = {0.0, 0.0};
 #define LFC_NITARGS , &fb, nit, gs
-#if LFC_COST_MODE == 1  // FP32 lockstep steps only (LFG_F32_FIRST counts them x 1000 in nit[0])
+// the FP32 opener's steps sit x 1000 in nit[0] (lfg_device.hpp); the lane and wave-max counts are FP64 steps
+#if LFC_COST_MODE == 1  // FP32 steps only
 #define LFC_COST(v) cost[v] = nit[0] / 1000
-#elif LFC_COST_MODE == 2  // everything else
-#define LFC_COST(v) cost[v] = nit[0] % 1000 + std::max(nit[1], nit[2]) + (fb ? 30 : 0)
-#else
-#define LFC_COST(v) cost[v] = nit[0] + std::max(nit[1], nit[2]) + (fb ? 30 : 0)
+#else  // FP64 steps: cone, then the longer of ingress and egress
+#define LFC_COST(v) cost[v] = nit[0] % 1000 + std::max(nit[1], nit[2]) + (fb ? 30 : 0); count2(0, nit[0] / 1000); count2(1, fb)
 #endif
 // element intervals in solve order (run with one thread to compare variants)
 static std::vector<double> g_ab;
@@ -258,7 +265,17 @@ void elements(const Pair& G, Tables& T)
         const double dx = -kDonCt[it], dy = kDonSt[it] * kDonCp[ip], dz = kDonSt[it] * kDonSp[ip];
         double lo = 0.0, hi = R.Rs, r = G.reff, gx, gy, gz;
         if (!(r > lo && r < hi)) r = 0.5 * hi;
+#if LFG_F32_OPEN && LFG_F32_ROOT_STEPS > 0
+        r = root_open32<LFG_F32_ROOT_STEPS>(R, dx, dy, dz, hi, r);
+#endif
+#ifdef LFC_COUNT
+        count2(2, 1);
+        count2(4, LFG_F32_OPEN ? LFG_F32_ROOT_STEPS : 0);
+#endif
         for (int itr = 0; itr < ROOT_MAXIT; ++itr) {
+#ifdef LFC_COUNT
+            count2(3, 1);
+#endif
             const double f = rpot_grad(R, std::fma(r, dx, 1.0), r * dy, r * dz, gx, gy, gz) - R.pl1;
             const double df = gx * dx + gy * dy + gz * dz;
             if (f > 0.0) hi = r; else lo = r;

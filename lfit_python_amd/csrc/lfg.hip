@@ -788,6 +788,9 @@ __device__ __forceinline__ void element_item_to(int v, GPtr G, Sink& K)
         const double dx = -ctc, dy = stc * kDonCp[ip], dz = stc * kDonSp[ip];
         double lo = 0.0, hi = R.Rs, r = G[G_REFF];
         if (!(r > lo && r < hi)) r = 0.5 * hi;
+#if LFG_F32_OPEN && LFG_F32_ROOT_STEPS > 0
+        r = root_open32<LFG_F32_ROOT_STEPS>(R, dx, dy, dz, hi, r);  // to ~1e-7 of the root in float
+#endif
         double gx, gy, gz;
         for (int itr = 0; itr < ROOT_MAXIT; ++itr) {
             const double X0 = fma(r, dx, 1.0), X1 = r * dy, X2 = r * dz;
@@ -853,8 +856,9 @@ __device__ __forceinline__ void element_item_to(int v, GPtr G, Sink& K)
         const int reg = (u < U_WD) ? 0 : (u < U_WD + U_DISC ? 1 : 2);
         unsigned long long* C = g_iter_dbg + reg * 16;
         for (int i = 0; i < 3; ++i) {
-            atomicAdd(C + i, (unsigned long long)nit[i]);
-            int m = nit[i];
+            const int ni = i ? nit[i] : nit[0] % 1000;  // (the FP32 opener's steps sit x 1000 in nit[0])
+            atomicAdd(C + i, (unsigned long long)ni);
+            int m = ni;
             for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
             if ((threadIdx.x & 63) == 0) atomicAdd(C + 3 + i, (unsigned long long)m);
         }

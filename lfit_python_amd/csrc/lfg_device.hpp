@@ -438,6 +438,9 @@ __device__ __forceinline__ void rotate(double& cs, double& sn, double d)
 // approach to D (~1e-2 off): with t that far off the second step's |dt| kept
 // a third step in play (tools/tol_study.py: k_elements' wave-max steps per
 // lane 4.27 -> 3.43 at config 2, interval errors < 3e-12 in phase).
+// With LFG_F32_OPEN (below) the Halley step and one Newton step are taken in
+// float first, and the FP64 loop here starts ~1e-7 rad from the contact:
+// wave-max FP64 steps 3.43 -> 2.04 at config 2, the same stopping rule.
 // Stop once |dth| <= TH_LAST (th error ~TH_LAST^2 after a Newton step) and
 // |dt| <= T_LAST (t errors reach th at second order): ~1e-12 rad (MODEL_SPEC 7).
 #ifndef LFG_TH_LAST
@@ -456,9 +459,10 @@ struct Tan {
 
 // one branch-free step (two solves can run interleaved in one lane);
 // HALLEY: the curvature-corrected first step
+// (halley: per lane, false where the float opener already took Halley's step)
 template <bool HALLEY = false>
 __device__ __forceinline__ void tangency_step(const Roche& R, double Px, double Py, double Pz, double s, double c,
-                                              bool ingress, Tan& T)
+                                              bool ingress, Tan& T, bool halley = true)
 {
     ConePt o;
     cone_point(R, Px, Py, Pz, s, c, T.cs, T.sn, T.t, o);
@@ -472,7 +476,7 @@ __device__ __forceinline__ void tangency_step(const Roche& R, double Px, double 
     const bool bad = !(J22 != 0.0) || !(den != 0.0);
     const double iden = rcp_step(den);
     double dth = -F1m * iden;
-    if (HALLEY) {  // dth / (1 + dth g'' / (2 g')); plain Newton where that factor is far from 1
+    if (HALLEY && halley) {  // dth / (1 + dth g'' / (2 g')); plain Newton where that factor is far from 1
         const double g2 = fma(T.t, fma(T.t, o.ethHeth, o.gtt), -J21 * J21 * iJ22);
         const double h = 0.5 * dth * g2 * iden;
         if (fabs(h) < 0.5) dth = dth * rcp_step(1.0 + h);
@@ -503,10 +507,10 @@ __device__ inline bool tangency(const Roche& R, double Px, double Py, double Pz,
 
 // ingress and egress in lockstep: two independent dependency chains per lane
 __device__ inline void tangency_pair(const Roche& R, double Px, double Py, double Pz, double s, double c, Tan& A,
-                                     Tan& B, int* nit = nullptr)
+                                     Tan& B, int* nit = nullptr, bool halleyA = true, bool halleyB = true)
 {
-    tangency_step<true>(R, Px, Py, Pz, s, c, true, A);  // both start running: no lockstep copies
-    tangency_step<true>(R, Px, Py, Pz, s, c, false, B);
+    tangency_step<true>(R, Px, Py, Pz, s, c, true, A, halleyA);  // both start running: no lockstep copies
+    tangency_step<true>(R, Px, Py, Pz, s, c, false, B, halleyB);
     if (nit) { nit[0] += 1; nit[1] += 1; }  // diagnostic builds only
     if (A.st != 0 && B.st != 0) return;
     for (int it = 1; it < 16; ++it) {
@@ -519,6 +523,212 @@ __device__ inline void tangency_pair(const Roche& R, double Px, double Py, doubl
         if (A.st != 0 && B.st != 0) break;
     }
 }
+
+// t at the ray's minimum of Phi, one Newton step from the closest approach
+// X_c to D: there the donor's own term has no slope along e, so
+// e.grad Phi = e.grad(-cA/r1 - (x-mu)^2 - y^2), and e.H.e = cB/d^3 + the
+// WD's and the centrifugal parts, with d = Rcal (the guess rays graze that
+// sphere); icb = cB / Rcal^3 - 2 s^2
+__device__ __forceinline__ void ray_min_prestep(const Roche& R, double Px, double Py, double Pz, double s, double c,
+                                                double icb, Tan& T)
+{
+    const double ex = s * T.cs, ey = -s * T.sn;
+    const double x = fma(T.t, ex, Px), y = fma(T.t, ey, Py), z = fma(T.t, c, Pz);
+    const double ir1 = rsqrt_pos(x * x + y * y + z * z), ir1s = ir1 * ir1;
+    const double eX = x * ex + y * ey + z * c;
+    const double i1 = R.cA * ir1s * ir1;
+    const double slope = fma(i1, eX, -2.0 * fma(x - R.mu, ex, y * ey));
+    const double curv = fma(i1, fma(-3.0 * eX * eX, ir1s, 1.0), icb);
+    T.t -= slope * rcp_fast(curv);
+}
+
+// ---------------------------------------------------------------------------
+// FP32 opener (LFG_F32_OPEN, default on; -DLFG_F32_OPEN=0 compiles none of it).
+// The Newton solves of the element phase need FP64 only for their last step:
+// an FP32 evaluation of F1 = Phi - Phi_L1 (|Phi| ~ 2..4) is good to ~3e-7,
+// which is a th error below TH_LAST and an r error of ~1e-7.  So the first
+// steps run in float, where a VALU instruction issues at twice the FP64 rate
+// and 1/x, 1/sqrt(x) are single instructions (v_rcp_f32, v_rsq_f32), and the
+// FP64 loops that follow, with their stopping rules unchanged, start ~1e-7
+// from the root: one FP64 step for a tangency, two for the donor radius.
+#ifndef LFG_F32_OPEN
+#define LFG_F32_OPEN 1
+#endif
+#ifndef LFG_F32_STEPS  // FP32 envelope steps per contact (the first is Halley's)
+#define LFG_F32_STEPS 2
+#endif
+// 1: an opened contact's first FP64 step is plain Newton, not Halley's (its
+// Halley step was the opener's first); k_pair at config 2: 37.0 us against 37.7
+#ifndef LFG_F32_NEWTON_AFTER
+#define LFG_F32_NEWTON_AFTER 1
+#endif
+// FP32 Newton steps opening the donor radius root; 0: none.  Three take its
+// FP64 steps from 4.4 to 2.1 a tile, but k_pair did not get shorter for it
+// (37.0 us against 37.2 without, inside the run-to-run spread): off
+#ifndef LFG_F32_ROOT_STEPS
+#define LFG_F32_ROOT_STEPS 0
+#endif
+
+#if LFG_F32_OPEN
+constexpr float F32_OPEN_MIN_WIDTH = 0.03f;  // rad (4.8e-3 in phase): narrower intervals are not opened in float
+// ingress and egress of one element side by side: a 2-vector on the device
+// (the compiler packs what it will into v_pk_*_f32), a plain struct on the host
+#ifdef __HIP__
+typedef float F2 __attribute__((ext_vector_type(2)));
+#else
+struct F2 {
+    float x, y;
+};
+inline F2 operator+(F2 a, F2 b) { return F2{a.x + b.x, a.y + b.y}; }
+inline F2 operator-(F2 a, F2 b) { return F2{a.x - b.x, a.y - b.y}; }
+inline F2 operator*(F2 a, F2 b) { return F2{a.x * b.x, a.y * b.y}; }
+inline F2 operator-(F2 a) { return F2{-a.x, -a.y}; }
+#endif
+__device__ __forceinline__ F2 f2(float a) { return F2{a, a}; }
+__device__ __forceinline__ F2 f2_rsq(F2 a) { return F2{__builtin_amdgcn_rsqf(a.x), __builtin_amdgcn_rsqf(a.y)}; }
+__device__ __forceinline__ F2 f2_rcp(F2 a) { return F2{__builtin_amdgcn_rcpf(a.x), __builtin_amdgcn_rcpf(a.y)}; }
+
+// N fixed FP32 envelope steps (tangency_step's, the first Halley's) for both
+// contacts of an element, from the sphere guesses with t at the closest
+// approach to D; the float twin of ray_min_prestep comes first.  No
+// convergence test: the FP64 solve that follows decides.  A contact whose
+// float steps left the envelope's valid range (non-finite, J22 <= 0, a step
+// or their sum over rotate's 0.05 rad, t <= 0, a narrow interval) is left at
+// its guess with the FP64 pre-step, the path without the opener (okA, okB
+// false).  Only sum(dth), t and the two flags leave this scope.
+template <int N>
+__device__ __forceinline__ void tangency_open32(const Roche& R, double Px, double Py, double Pz, double s, double c,
+                                                double Rcal, Tan& A, Tan& B, bool& okA, bool& okB)
+{
+    float dA, dB, tA, tB;
+    okA = okB = true;
+    {
+        const float cA = float(R.cA), cB = float(R.cB), mu = float(R.mu), pl1 = float(R.pl1);
+        const F2 px = f2(float(Px)), py = f2(float(Py)), pz = f2(float(Pz)), sf = f2(float(s)), cf = f2(float(c));
+        const float rc = float(Rcal);
+        const F2 icb = f2(cB * __builtin_amdgcn_rcpf(rc * rc * rc)) - f2(2.0f) * sf * sf;
+        F2 cs{float(A.cs), float(B.cs)}, sn{float(A.sn), float(B.sn)}, t{float(A.t), float(B.t)};
+        F2 sum = f2(0.0f);
+        {  // ray_min_prestep
+            const F2 ex = sf * cs, ey = -(sf * sn);
+            const F2 x = t * ex + px, y = t * ey + py, z = t * cf + pz;
+            const F2 ir1 = f2_rsq(x * x + y * y + z * z), ir1s = ir1 * ir1;
+            const F2 eX = x * ex + y * ey + z * cf;
+            const F2 i1 = f2(cA) * ir1s * ir1;
+            const F2 slope = i1 * eX - f2(2.0f) * ((x - f2(mu)) * ex + y * ey);
+            const F2 curv = i1 * (f2(1.0f) - f2(3.0f) * eX * eX * ir1s) + icb;
+            t = t - slope * f2_rcp(curv);
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            // cone_point
+            const F2 ex = sf * cs, ey = -(sf * sn);
+            const F2 x = t * ex + px, y = t * ey + py, z = t * cf + pz;
+            const F2 yz = y * y + z * z;
+            const F2 ir1 = f2_rsq(x * x + yz), ir1s = ir1 * ir1;
+            const F2 dx = x - f2(1.0f);
+            const F2 ir2 = f2_rsq(dx * dx + yz), ir2s = ir2 * ir2;
+            const F2 i1 = f2(cA) * ir1s * ir1, i2 = f2(cB) * ir2s * ir2, i12 = i1 + i2;
+            const F2 xm = x - f2(mu);
+            const F2 F1 = -(f2(cA) * ir1) - f2(cB) * ir2 - xm * xm - y * y - f2(pl1);
+            const F2 gx = i1 * x + i2 * dx - f2(2.0f) * xm;
+            const F2 gy = (i12 - f2(2.0f)) * y;
+            const F2 gz = i12 * z;
+            const F2 p1 = x * ex + y * ey + z * cf, p2 = p1 - ex;
+            const F2 q1 = x * ey - y * ex, q2 = q1 - ey;
+            const F2 k1 = f2(3.0f) * i1 * ir1s, k2 = f2(3.0f) * i2 * ir2s;
+            const F2 s2 = ex * ex + ey * ey;
+            const F2 Ft = gx * ex + gy * ey + gz * cf;
+            const F2 gth = gx * ey - gy * ex;
+            const F2 J22 = i12 - k1 * p1 * p1 - k2 * p2 * p2 - f2(2.0f) * s2;
+            const F2 etHe = -(k1 * p1 * q1) - k2 * p2 * q2;
+            // tangency_step
+            const F2 J11 = t * gth, J21 = t * etHe + gth;
+            const F2 iJ22 = f2_rcp(J22);
+            const F2 dt0 = -(Ft * iJ22);
+            const F2 F1m = f2(0.5f) * Ft * dt0 + F1;
+            const F2 iden = f2_rcp(J21 * dt0 + J11);
+            F2 dth = -(F1m * iden);
+            if (k == 0) {
+                const F2 ethHeth = i12 * s2 - k1 * q1 * q1 - k2 * q2 * q2 - f2(2.0f) * s2;
+                const F2 gtt = -(gx * ex + gy * ey);
+                const F2 g2 = t * (t * ethHeth + gtt) - J21 * J21 * iJ22;
+                const F2 h = f2(0.5f) * dth * g2 * iden;
+                const F2 dh = dth * f2_rcp(f2(1.0f) + h);
+                dth = F2{fabsf(h.x) < 0.5f ? dh.x : dth.x, fabsf(h.y) < 0.5f ? dh.y : dth.y};
+            }
+            okA = okA && J22.x > 0.0f && fabsf(dth.x) <= 0.05f;  // (non-finite values fail the comparisons)
+            okB = okB && J22.y > 0.0f && fabsf(dth.y) <= 0.05f;
+            t = t + (dt0 - J21 * iJ22 * dth);
+            sum = sum + dth;
+            // rotate: Taylor series, error < 2e-13 at 0.05 rad
+            const F2 d2 = dth * dth;
+            const F2 sd = dth * (f2(1.0f) - d2 * f2(1.0f / 6.0f) * (f2(1.0f) - d2 * f2(1.0f / 20.0f)));
+            const F2 cd = f2(1.0f) - d2 * f2(0.5f) * (f2(1.0f) - d2 * f2(1.0f / 12.0f) *
+                                                                  (f2(1.0f) - d2 * f2(1.0f / 30.0f)));
+            const F2 c2 = cs * cd - sn * sd;
+            sn = sn * cd + cs * sd;
+            cs = c2;
+        }
+        // a narrow interval is a nearly double root of the envelope: g''/g' ~
+        // 2 / width, and float's rounding of F1 over a slope that small lands
+        // outside the last FP64 step's quadratic reach (below ~3e-3 in phase
+        // the answers moved by up to 4e-11); those keep the FP64 path
+        const bool wide = float(B.th - A.th) + (sum.y - sum.x) >= F32_OPEN_MIN_WIDTH;
+        okA = okA && wide && fabsf(sum.x) <= 0.05f && t.x > 0.0f && t.x < 3.0e38f;
+        okB = okB && wide && fabsf(sum.y) <= 0.05f && t.y > 0.0f && t.y < 3.0e38f;
+        dA = okA ? sum.x : 0.0f;
+        dB = okB ? sum.y : 0.0f;
+        tA = t.x;
+        tB = t.y;
+    }
+    // the FP64 state moves once (a rotation by 0 is exact)
+    A.th += double(dA);
+    B.th += double(dB);
+    rotate(A.cs, A.sn, double(dA));
+    rotate(B.cs, B.sn, double(dB));
+    A.t = double(tA);
+    B.t = double(tB);
+    if (!(okA && okB)) {  // rare: the start without the opener for the contact that bailed out
+        // (its t at the closest approach to D is worked out again here, so
+        // that no FP64 t stays live across the float steps)
+        const double icb = R.cB / (Rcal * Rcal * Rcal) - 2.0 * s * s;
+        for (int k = 0; k < 2; ++k) {
+            Tan& T = k ? B : A;
+            if (k ? okB : okA) continue;
+            T.t = s * ((1.0 - Px) * T.cs + Py * T.sn) - Pz * c;
+            ray_min_prestep(R, Px, Py, Pz, s, c, icb, T);
+        }
+    }
+}
+
+// N FP32 Newton steps of the donor radius root F(r) = Phi(D + r d) - Phi_L1
+// from r0 inside (0, hi); r0 itself unless every step kept dF/dr > 0 and
+// stayed inside.  The FP64 loop that follows keeps its own bracket: a float
+// sign of F next to the root says nothing about which side it is on.
+template <int N>
+__device__ __forceinline__ double root_open32(const Roche& R, double dx, double dy, double dz, double hi, double r0)
+{
+    const float cA = float(R.cA), cB = float(R.cB), mu = float(R.mu), pl1 = float(R.pl1);
+    const float ax = float(dx), ay = float(dy), az = float(dz), top = float(hi);
+    float r = float(r0);
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const float x = fmaf(r, ax, 1.0f), y = r * ay, z = r * az, x1 = r * ax;
+        const float yz = y * y + z * z;
+        const float ir1 = __builtin_amdgcn_rsqf(x * x + yz), ir2 = __builtin_amdgcn_rsqf(x1 * x1 + yz);
+        const float i1 = cA * ir1 * ir1 * ir1, i2 = cB * ir2 * ir2 * ir2;
+        const float xm = x - mu;
+        const float f = -cA * ir1 - cB * ir2 - xm * xm - y * y - pl1;
+        const float gx = i1 * x + i2 * x1 - 2.0f * xm, gy = (i1 + i2 - 2.0f) * y, gz = (i1 + i2) * z;
+        const float df = gx * ax + gy * ay + gz * az;
+        r -= f * __builtin_amdgcn_rcpf(df);
+        ok = ok && df > 0.0f && r > 0.0f && r < top;
+    }
+    return ok ? double(r) : r0;
+}
+#endif  // LFG_F32_OPEN
 
 // 0: not eclipsed, 1: eclipsed, -1: undecided (use the nested solver)
 __device__ inline int cone_exists(const Roche& R, double Px, double Py, double Pz, double s, double c,
@@ -593,25 +803,24 @@ __device__ inline bool element_interval_fast(const Roche& R, double Px, double P
                 Tan In{thc - de, ci, si, s * (ux * ci - uy * si) + uz * c, 0};
                 Tan Out{thc + de, co, so, s * (ux * co - uy * so) + uz * c, 0};
                 if (guess) { guess[0] = In.th; guess[1] = Out.th; }  // diagnostic builds only
-                // t at the ray's minimum of Phi, one Newton step from the
-                // closest approach X_c to D: there the donor's own term has
-                // no slope along e, so e.grad Phi = e.grad(-cA/r1 - (x-mu)^2
-                // - y^2), and e.H.e = cB/d^3 + the WD's and the centrifugal
-                // parts, with d = Rcal (the guess rays graze that sphere)
-                {
+#if LFG_F32_OPEN
+                // t to the ray's minimum of Phi and LFG_F32_STEPS envelope steps, in float
+                bool openIn, openOut;
+                tangency_open32<LFG_F32_STEPS>(R, Px, Py, Pz, s, c, Rcal, In, Out, openIn, openOut);
+                if (nit) nit[0] += 1000 * LFG_F32_STEPS;  // diagnostic builds only: FP32 steps count x 1000
+                // an opened contact has had its Halley step in float: plain Newton from its first FP64 step on
+                const bool hIn = !(LFG_F32_NEWTON_AFTER && openIn), hOut = !(LFG_F32_NEWTON_AFTER && openOut);
+#else
+                {  // t at the ray's minimum of Phi (ray_min_prestep)
                     const double icb = R.cB / (Rcal * Rcal * Rcal) - 2.0 * s * s;
-                    for (Tan* T : {&In, &Out}) {
-                        const double ex = s * T->cs, ey = -s * T->sn;
-                        const double x = fma(T->t, ex, Px), y = fma(T->t, ey, Py), z = fma(T->t, c, Pz);
-                        const double ir1 = rsqrt_pos(x * x + y * y + z * z), ir1s = ir1 * ir1;
-                        const double eX = x * ex + y * ey + z * c;
-                        const double i1 = R.cA * ir1s * ir1;
-                        const double slope = fma(i1, eX, -2.0 * fma(x - R.mu, ex, y * ey));
-                        const double curv = fma(i1, fma(-3.0 * eX * eX, ir1s, 1.0), icb);
-                        T->t -= slope * rcp_fast(curv);
-                    }
+                    for (Tan* T : {&In, &Out}) ray_min_prestep(R, Px, Py, Pz, s, c, icb, *T);
                 }
+#endif
+#if LFG_F32_OPEN
+                tangency_pair(R, Px, Py, Pz, s, c, In, Out, nit ? nit + 1 : nullptr, hIn, hOut);
+#else
                 tangency_pair(R, Px, Py, Pz, s, c, In, Out, nit ? nit + 1 : nullptr);
+#endif
                 // both contacts within Dm of thc (where the ray meets the
                 // donor's sphere), tested as cos(th - thc) > cos Dm with the
                 // rotated cosines: no acos; the steps are clamped to 0.05 rad

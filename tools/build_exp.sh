@@ -16,5 +16,6 @@ if [ "${LFG_SPLIT:-1}" = 1 ]; then
   split="-x none $R/build/exp/split_$name.o"
 fi
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -I $R/include "$@" \
-  -o $R/build/exp/liblfg_$name.so ${LFG_SRC:-$R/lfit_python_amd/csrc/lfg.hip} $R/lfit_python_amd/csrc/lfg_components.hip $split
+  -o $R/build/exp/liblfg_$name.so ${LFG_SRC:-$R/lfit_python_amd/csrc/lfg.hip} $R/lfit_python_amd/csrc/lfg_components.hip \
+  $R/lfit_python_amd/csrc/lfg_pt.hip $R/lfit_python_amd/csrc/lfg_gp_predict.hip $split
 rm -f $R/build/exp/split_$name.o

@@ -4,6 +4,10 @@ a k_elements wave runs (the max over its 64 lanes), on the host build of the
 GPU algorithm (cpu_baseline/lfg_cpu.cpp -DLFC_COUNT).
 
     python tools/tol_study.py [--walkers 256] [--config 2|3|5] th:t[:pth:pt][+DEFINE...] ...
+
+The steps counted are FP64 ones; the FP32 opener's (LFG_F32_OPEN) and the
+donor radius root's are printed beside them.  A/B of the opener:
+    python tools/tol_study.py 1e-6:3e-5+LFG_F32_OPEN=0 1e-6:3e-5 1e-6:3e-5+LFG_F32_STEPS=3
 """
 import argparse
 import ctypes
@@ -54,6 +58,7 @@ def main():
         extra = ["-DLFG_NEWTON_PRED", "-DLFG_PRED_TH=%s" % spec.split(":")[2], "-DLFG_PRED_T=%s" % spec.split(":")[3]] \
             if spec.count(":") == 3 else []
         extra += ["-D" + f for f in flags]
+        os.makedirs("/tmp/tol", exist_ok=True)
         out = "/tmp/tol/liblfc_%s.so" % v.replace(":", "_").replace("+", "_")
         build(th, tt, out, extra)
         P = cpu.CpuPort(out)
@@ -62,6 +67,8 @@ def main():
         dt = time.perf_counter() - t0
         c = (ctypes.c_ulonglong * 28)()
         P.lib.lfc_counts(c)
+        c2 = (ctypes.c_ulonglong * 5)()
+        P.lib.lfc_counts2(c2)
         hist = np.array(c[4:]).reshape(3, 8)
         hist = "  ".join("%s %s" % (r, np.round(h / max(h.sum(), 1), 3)[1:7]) for r, h in zip(("wd", "disc", "spot"), hist))
         assert np.array_equal(np.isfinite(got), fin)
@@ -78,6 +85,8 @@ def main():
         err = np.abs(got[fin] - ref[fin]) / np.abs(ref[fin])
         print("%-24s lnp err max %.1e med %.1e | steps/lane %.3f  wave-max %.3f"
               "  | %s\n    lane steps 1..6: %s" % (v, err.max(), np.median(err), c[1] / c[0], c[3] / c[2], dab, hist))
+        print("    FP32 steps/lane %.2f  fallbacks %d  donor root steps/tile FP64 %.2f FP32 %.2f"
+              % (c2[0] / max(c[0], 1), c2[1], c2[3] / max(c2[2], 1), c2[4] / max(c2[2], 1)))
 
 
 if __name__ == "__main__":
