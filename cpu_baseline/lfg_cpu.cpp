@@ -199,6 +199,11 @@ extern "C" long lfc_dump_guess(double* o, long n)
     g_gs.clear();
     return m;
 }
+// unit_dir (lfg_device.hpp) on n angles: ok[i] = 0 where it reports out of range (cs, sn untouched there)
+extern "C" void lfc_unit_dir(const double* th, long n, double* cs, double* sn, int* ok)
+{
+    for (long i = 0; i < n; ++i) ok[i] = unit_dir(th[i], cs[i], sn[i]) ? 1 : 0;
+}
 #else
 #define LFC_NIT
 #define LFC_NITARGS

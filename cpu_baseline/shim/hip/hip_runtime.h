@@ -14,6 +14,7 @@
 #define __builtin_amdgcn_rcp(x) (1.0 / (x))
 #define __builtin_amdgcn_rsqf(x) (1.0f / std::sqrt(float(x)))  // v_rsq_f32 / v_rcp_f32 of the FP32 opener
 #define __builtin_amdgcn_rcpf(x) (1.0f / float(x))
+#define __builtin_amdgcn_sqrtf(x) std::sqrt(float(x))  // v_sqrt_f32 of the float guess
 using std::max;  // the device code's integer min / max
 using std::min;
 inline double rsqrt(double x) { return 1.0 / std::sqrt(x); }

@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "lfg_stream_table.h"
+#include "lfg_tables.hpp"  // kUnitCos, kUnitSin (unit_dir)
 
 namespace lfg {
 
@@ -419,6 +420,35 @@ __device__ __forceinline__ void rotate(double& cs, double& sn, double d)
     cs = c2;
 }
 
+// Tabulated start of the tangency solves (LFG_TAB_START, default on;
+// -DLFG_TAB_START=0 compiles the FP64 guess block of before).  The sphere
+// guess of element_interval_fast is only a start that the solve moves by
+// 1e-3..1e-2 rad: its angles and directions are formed in float, and the one
+// thing that has to be exact, that the running angle T.th and the running
+// direction (T.cs, T.sn) describe the same angle, is made so once, where the
+// FP64 state is formed: unit_dir(th) is (cos, sin)(th) to ~6e-16 from the
+// nearest entry of a table in steps of 1/16 rad (kUnitCos, kUnitSin: 0..5 rad,
+// correctly rounded) and one rotate() by at most 1/32 rad.  No FP64 atan2,
+// acos, sqrt or quotient serves the guess.
+#ifndef LFG_TAB_START
+#define LFG_TAB_START 1
+#endif
+constexpr double UNIT_MAX = 5.0;  // rad: kUnitCos / kUnitSin reach k = 80
+static_assert(sizeof(kUnitCos) / sizeof(double) == 81 && sizeof(kUnitSin) / sizeof(double) == 81, "UNIT_MAX * 16 + 1");
+
+// false, with nothing read, unless th is finite and |th| <= UNIT_MAX (the
+// index is formed only from a value that passed that test)
+__device__ __forceinline__ bool unit_dir(double th, double& cs, double& sn)
+{
+    if (!(fabs(th) <= UNIT_MAX)) return false;  // (NaN fails the comparison)
+    const double kf = rint(th * 16.0);
+    const int k = min(int(fabs(kf)), 80);  // cos even, sin odd
+    cs = kUnitCos[k];
+    sn = kf < 0.0 ? -kUnitSin[k] : kUnitSin[k];
+    rotate(cs, sn, fma(kf, -0.0625, th));  // exact: th within a factor 2 of kf / 16, or kf = 0
+    return true;
+}
+
 // 2-D Newton for one contact phase.  Tan holds the running angle th, its
 // cosine and sine (advanced by rotation), the distance t along the line of
 // sight and the state: 0 running, 1 converged to a tangency of the right kind
@@ -595,19 +625,20 @@ __device__ __forceinline__ F2 f2_rcp(F2 a) { return F2{__builtin_amdgcn_rcpf(a.x
 // float steps left the envelope's valid range (non-finite, J22 <= 0, a step
 // or their sum over rotate's 0.05 rad, t <= 0, a narrow interval) is left at
 // its guess with the FP64 pre-step, the path without the opener (okA, okB
-// false).  Only sum(dth), t and the two flags leave this scope.
+// false).  The guess comes in as float directions (cs, sn), t and the width
+// th_B - th_A; only sum(dth) (0 for a contact that bailed out), t and the two
+// flags leave this scope: the caller forms the FP64 state from them.
 template <int N>
-__device__ __forceinline__ void tangency_open32(const Roche& R, double Px, double Py, double Pz, double s, double c,
-                                                double Rcal, Tan& A, Tan& B, bool& okA, bool& okB)
+__device__ __forceinline__ void tangency_open32_steps(const Roche& R, double Px, double Py, double Pz, double s,
+                                                      double c, double Rcal, F2 cs, F2 sn, F2 t, float width,
+                                                      float& dA, float& dB, float& tA, float& tB, bool& okA, bool& okB)
 {
-    float dA, dB, tA, tB;
     okA = okB = true;
     {
         const float cA = float(R.cA), cB = float(R.cB), mu = float(R.mu), pl1 = float(R.pl1);
         const F2 px = f2(float(Px)), py = f2(float(Py)), pz = f2(float(Pz)), sf = f2(float(s)), cf = f2(float(c));
         const float rc = float(Rcal);
         const F2 icb = f2(cB * __builtin_amdgcn_rcpf(rc * rc * rc)) - f2(2.0f) * sf * sf;
-        F2 cs{float(A.cs), float(B.cs)}, sn{float(A.sn), float(B.sn)}, t{float(A.t), float(B.t)};
         F2 sum = f2(0.0f);
         {  // ray_min_prestep
             const F2 ex = sf * cs, ey = -(sf * sn);
@@ -674,7 +705,7 @@ __device__ __forceinline__ void tangency_open32(const Roche& R, double Px, doubl
         // 2 / width, and float's rounding of F1 over a slope that small lands
         // outside the last FP64 step's quadratic reach (below ~3e-3 in phase
         // the answers moved by up to 4e-11); those keep the FP64 path
-        const bool wide = float(B.th - A.th) + (sum.y - sum.x) >= F32_OPEN_MIN_WIDTH;
+        const bool wide = width + (sum.y - sum.x) >= F32_OPEN_MIN_WIDTH;
         okA = okA && wide && fabsf(sum.x) <= 0.05f && t.x > 0.0f && t.x < 3.0e38f;
         okB = okB && wide && fabsf(sum.y) <= 0.05f && t.y > 0.0f && t.y < 3.0e38f;
         dA = okA ? sum.x : 0.0f;
@@ -682,6 +713,18 @@ __device__ __forceinline__ void tangency_open32(const Roche& R, double Px, doubl
         tA = t.x;
         tB = t.y;
     }
+}
+
+#if !LFG_TAB_START
+// the opener from an FP64 guess (A, B: th, its direction, t at the closest
+// approach to D), which it moves by the float steps
+template <int N>
+__device__ __forceinline__ void tangency_open32(const Roche& R, double Px, double Py, double Pz, double s, double c,
+                                                double Rcal, Tan& A, Tan& B, bool& okA, bool& okB)
+{
+    float dA, dB, tA, tB;
+    tangency_open32_steps<N>(R, Px, Py, Pz, s, c, Rcal, F2{float(A.cs), float(B.cs)}, F2{float(A.sn), float(B.sn)},
+                             F2{float(A.t), float(B.t)}, float(B.th - A.th), dA, dB, tA, tB, okA, okB);
     // the FP64 state moves once (a rotation by 0 is exact)
     A.th += double(dA);
     B.th += double(dB);
@@ -701,6 +744,7 @@ __device__ __forceinline__ void tangency_open32(const Roche& R, double Px, doubl
         }
     }
 }
+#endif  // !LFG_TAB_START
 
 // N FP32 Newton steps of the donor radius root F(r) = Phi(D + r d) - Phi_L1
 // from r0 inside (0, hi); r0 itself unless every step kept dF/dr > 0 and
@@ -759,7 +803,11 @@ __device__ inline int cone_exists(const Roche& R, double Px, double Py, double P
 }
 
 // element_interval with the fast path; Rcal = sphere radius reproducing the
-// WD-centre contact (initial guesses only).  Trig: one atan2 and one acos.
+// WD-centre contact (initial guesses only).  Whether an element is eclipsed
+// (cosD, the closest-approach potential, cone_exists, the final bound on both
+// contacts) is decided in FP64.  Trig: one atan2f and one acosf for the guess
+// angles, and two table reads (unit_dir) for the FP64 directions; with
+// -DLFG_TAB_START=0 one FP64 atan2 and one FP64 acos.
 __device__ inline bool element_interval_fast(const Roche& R, double Px, double Py, double Pz, double s,
                                              double c, double Rcal, double Reff, double& a, double& b,
                                              bool* fallback = nullptr, int* nit = nullptr, double* guess = nullptr)
@@ -792,6 +840,63 @@ __device__ inline bool element_interval_fast(const Roche& R, double Px, double P
             }
         }
         if (ex == 0) { a = 1.0; b = -1.0; return false; }
+#if LFG_TAB_START
+        if (ex == 1) {
+            // the sphere guess in float: thc -+ de with cos de = ce, the
+            // directions cc ce +- sc se from the same float values (they agree
+            // with their float angles to float rounding, ~2e-7), t at the
+            // closest approach to D along each ray
+            const float pxf = float(Px), pyf = float(Py), pzf = float(Pz), sf = float(s), cf = float(c);
+            const float rcf = float(Rcal);
+            const float uxf = 1.0f - pxf, uxy2f = uxf * uxf + pyf * pyf, uuf = uxy2f + pzf * pzf;
+            const float iuf = __builtin_amdgcn_rsqf(uxy2f);
+            const float ccf = uxf * iuf, scf = pyf * iuf;
+            const float cef = (__builtin_amdgcn_sqrtf(fmaxf(uuf - rcf * rcf, 0.0f)) + cf * pzf) * iuf *
+                              __builtin_amdgcn_rcpf(sf);
+            if (cef > -1.0f && cef < 1.0f) {
+                const float sef = __builtin_amdgcn_sqrtf(1.0f - cef * cef);
+                const float thcf = atan2f(scf, ccf), def = acosf(cef);
+                const float thi = thcf - def, tho = thcf + def;
+                const float ci = ccf * cef + scf * sef, si = scf * cef - ccf * sef;
+                const float co = ccf * cef - scf * sef, so = scf * cef + ccf * sef;
+                const float ti = sf * (uxf * ci + pyf * si) - pzf * cf, to = sf * (uxf * co + pyf * so) - pzf * cf;
+                if (guess) { guess[0] = double(thi); guess[1] = double(tho); }  // diagnostic builds only
+                float dIn = 0.0f, dOut = 0.0f, tIn = 0.0f, tOut = 0.0f;
+                bool openIn = false, openOut = false;
+#if LFG_F32_OPEN
+                // t to the ray's minimum of Phi and LFG_F32_STEPS envelope steps, in float
+                tangency_open32_steps<LFG_F32_STEPS>(R, Px, Py, Pz, s, c, Rcal, F2{ci, co}, F2{si, so}, F2{ti, to},
+                                                     tho - thi, dIn, dOut, tIn, tOut, openIn, openOut);
+                if (nit) nit[0] += 1000 * LFG_F32_STEPS;  // diagnostic builds only: FP32 steps count x 1000
+#endif
+                // the FP64 state, formed once: the angle, and its direction from the table
+                Tan In{double(thi) + double(dIn), 1.0, 0.0, double(tIn), 0};
+                Tan Out{double(tho) + double(dOut), 1.0, 0.0, double(tOut), 0};
+                // (an angle outside the table's range: the nested solver)
+                if (unit_dir(In.th, In.cs, In.sn) && unit_dir(Out.th, Out.cs, Out.sn)) {
+                    if (!(openIn && openOut)) {  // rare with the opener: the FP64 start of a contact it left at its guess
+                        const double icb = R.cB / (Rcal * Rcal * Rcal) - 2.0 * s * s;
+                        for (int k = 0; k < 2; ++k) {
+                            Tan& T = k ? Out : In;
+                            if (k ? openOut : openIn) continue;
+                            T.t = s * (ux * T.cs - uy * T.sn) + uz * c;
+                            ray_min_prestep(R, Px, Py, Pz, s, c, icb, T);
+                        }
+                    }
+                    // an opened contact has had its Halley step in float: plain Newton from its first FP64 step on
+                    const bool hIn = !(LFG_F32_NEWTON_AFTER && openIn), hOut = !(LFG_F32_NEWTON_AFTER && openOut);
+                    tangency_pair(R, Px, Py, Pz, s, c, In, Out, nit ? nit + 1 : nullptr, hIn, hOut);
+                    // both contacts within Dm of thc, as cos(th - thc) > cos Dm (below)
+                    const double cin = In.cs * cc + In.sn * sc, cout = Out.cs * cc + Out.sn * sc;
+                    if (In.st == 1 && Out.st == 1 && In.th < Out.th && cin > cosD && cout > cosD) {
+                        a = In.th * (1.0 / TWO_PI);
+                        b = Out.th * (1.0 / TWO_PI);
+                        return true;
+                    }
+                }
+            }
+        }
+#else
         if (ex == 1) {
             const double ce = (sqrt(fmax(uu - Rcal * Rcal, 0.0)) - c * uz) * iuxy / s;
             if (ce > -1.0 && ce < 1.0) {
@@ -833,6 +938,7 @@ __device__ inline bool element_interval_fast(const Roche& R, double Px, double P
                 }
             }
         }
+#endif  // LFG_TAB_START
     }
     if (fallback) *fallback = true;
     return element_interval(R, Px, Py, Pz, s, c, Reff, a, b);
