@@ -31,11 +31,9 @@ SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "
 # without machine LICM (the reason: lfg.hip, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
 SPLIT_FLAGS = ["-mllvm", "-disable-machine-licm"]
-HEADERS = [os.path.join(_HERE, "csrc", "lfg_device.hpp"),
-           os.path.join(_HERE, "csrc", "lfg_tables.hpp"),
-           os.path.join(_HERE, "csrc", "lfg_stream_table.h"),
-           os.path.join(_HERE, "csrc", "lfg_philox.hpp"),
-           os.path.join(REPO, "include", "lfg.h")]
+# every header a unit can include: whatever csrc/ holds, and the C ABI
+HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
+                 if f.endswith((".hpp", ".h"))) + [os.path.join(REPO, "include", "lfg.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 

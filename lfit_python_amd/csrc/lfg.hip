@@ -27,11 +27,11 @@
 
 using namespace lfg;
 
-// Diagnostic builds that read device counters back (lfg_debug_*) keep every
-// kernel in this translation unit (see lfg_pair_launch_split below)
-#if defined(LFG_PROFILE_PAIR) || defined(LFG_COUNT_ITERS) || defined(LFG_COUNT_QUIET)
-#define LFG_ONE_TU 1
-#endif
+// Diagnostic builds that read device counters back (lfg_debug_*,
+// lfg_diag_iters) keep every kernel in this translation unit (see
+// lfg_pair_launch_split below): LFG_ONE_TU, by the one rule of lfg_diag.hpp,
+// which lfg_pair_split.hip sees through this file
+#include "lfg_diag.hpp"
 
 namespace {
 
@@ -5238,6 +5238,12 @@ __global__ void k_roche(int op, const double* __restrict__ a, const double* __re
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? LFG_OK : LFG_E_LAUNCH; }
 
 #ifndef LFG_NOLICM_TU
+// record event i of ev (nullable, LFG_NEV events, each nullable) on the stream
+inline void mark_event(void* const* ev, int i, hipStream_t st)
+{
+    if (ev && ev[i]) (void)hipEventRecord(static_cast<hipEvent_t>(ev[i]), st);
+}
+
 // k_setup (setup, prior and stream lanes) then k_elements, on the caller's
 // stream.  ev (nullable, LFG_NEV events): 0 before k_setup, 1 after k_setup,
 // 2 after k_elements
@@ -5245,17 +5251,14 @@ inline int launch_ok() { return hipGetLastError() == hipSuccess ? LFG_OK : LFG_E
 int run_front(const SetupArgs& S, const Ws& ws, hipStream_t st, void* const* ev, bool elements = true,
               const ElemSpec* X = nullptr, bool setup = true)
 {
-    auto mark = [&](int i) {
-        if (ev && ev[i]) (void)hipEventRecord(static_cast<hipEvent_t>(ev[i]), st);
-    };
     const int npairs = S.W * S.E;
     const int nlanes = 2 * npairs + S.W;
-    mark(0);
+    mark_event(ev, 0, st);
     if (setup) {
         hipLaunchKernelGGL(k_setup, dim3((nlanes + SETUP_BLOCK - 1) / SETUP_BLOCK), dim3(SETUP_BLOCK), 0, st, S);
         if (launch_ok() != LFG_OK) return LFG_E_LAUNCH;
     }
-    mark(1);
+    mark_event(ev, 1, st);
     if (elements) {
         constexpr int chunks = (NUNIQ + ELEM_BLOCK * LFG_ELEM_IPL - 1) / (ELEM_BLOCK * LFG_ELEM_IPL);
         ElemSpec none{};
@@ -5264,7 +5267,7 @@ int run_front(const SetupArgs& S, const Ws& ws, hipStream_t st, void* const* ev,
                            st, ws.geo, ws.status, npairs, ws.ab, ws.donor, ws.wts, ws.bstatus, XS);
         if (launch_ok() != LFG_OK) return LFG_E_LAUNCH;
     }
-    mark(2);
+    mark_event(ev, 2, st);
     return LFG_OK;
 }
 #endif  // LFG_NOLICM_TU
@@ -5315,6 +5318,44 @@ size_t lfg_workspace_size_tree(int W, const lfg_tree* T)
     return carve(nullptr, W, T->E, T->gp ? T->max_n : 0, T->ndim).total;  // + lfg_stretch_step_half_spec's
 }
 
+// k_setup's arguments for a flat batch: W vectors of P eclipse parameters,
+// one eclipse each, no tree (lfg_flux, lfg_lnlike, lfg_elements)
+static SetupArgs setup_args_flat(const double* pars, int W, int P, const Ws& ws)
+{
+    SetupArgs S{};
+    S.walkers = pars;
+    S.W = W;
+    S.ndim = P;
+    S.E = 1;
+    S.P = P;
+    S.geo = ws.geo;
+    S.status = ws.status;
+    S.prior = ws.prior;
+    S.bstatus = ws.bstatus;
+    return S;
+}
+
+// the likelihood kernels' arguments for such a batch: every pair on the
+// points x[0..N) of widths w; the caller adds its outputs (flux and comps,
+// or y, ye and lle)
+static LikeArgs like_args_flat(const Ws& ws, int W, const double* x, const double* w, int N, int nsub)
+{
+    LikeArgs L{};
+    L.geo = ws.geo;
+    L.status = ws.status;
+    L.AB = ws.ab;
+    L.DON = ws.donor;
+    L.WT = ws.wts;
+    L.E = 1;
+    L.N = N;
+    L.x = x;
+    L.w = w;
+    L.nsub = nsub;
+    L.npairs = W;
+    L.bstatus = ws.bstatus;
+    return L;
+}
+
 int lfg_flux(const double* pars, int W, int P, const double* x, const double* w, int N, int nsub,
              double* flux, double* comps, int* status, void* wsp, size_t ws_bytes, void* stream)
 {
@@ -5322,15 +5363,13 @@ int lfg_flux(const double* pars, int W, int P, const double* x, const double* w,
     Ws ws = carve(wsp, W, 1);
     if (!wsp || ws_bytes < ws.total) return LFG_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SetupArgs S{pars, W, P, 1, P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                ws.geo, ws.status, ws.prior, ws.bstatus, 0, nullptr, nullptr};
+    const SetupArgs S = setup_args_flat(pars, W, P, ws);
     int rc = run_front(S, ws, st, nullptr);
     if (rc) return rc;
     if (N > 0) {
-        LikeArgs L{ws.geo, ws.status, ws.ab, ws.donor, ws.wts, 1, nullptr, N, x, nullptr, nullptr, w,
-                   nsub, flux, comps, nullptr, W, nullptr, nullptr, nullptr, false, nullptr,
-                   nullptr, nullptr, nullptr, 0, 0, 0ull, 0ull, nullptr};
-        L.bstatus = ws.bstatus;
+        LikeArgs L = like_args_flat(ws, W, x, w, N, nsub);
+        L.flux = flux;
+        L.comps = comps;
         if (nsub > 1) hipLaunchKernelGGL((k_lnlike<0, true>), dim3(W), dim3(LIKE_THREADS), 0, st, L);
         else hipLaunchKernelGGL((k_lnlike<0, false>), dim3(W), dim3(LIKE_THREADS), 0, st, L);
         if ((rc = launch_ok())) return rc;
@@ -5367,6 +5406,19 @@ static int pair_eligible(int gp, int nsub, int max_n, int ndim)
 {
     if (pair_fits(nsub, max_n, ndim)) return 1;
     return (!gp && nsub >= 1 && ndim <= LIKE_THREADS) ? 2 : 0;
+}
+
+// k_pair's arguments but for the proposal and fold fields (pair_args_move):
+// nbc blocks per candidate carry the speculative lanes, a whole wave each
+static PairArgs pair_args(const LikeArgs& L, const ElemSpec& X, int nbc, int npairs)
+{
+    PairArgs A{};
+    A.L = L;
+    A.X = X;
+    A.spl = 64;
+    A.nbc = nbc;
+    A.prio = pair_prio(npairs);
+    return A;
 }
 
 static bool pair_env()
@@ -5410,17 +5462,16 @@ int lfg_lnlike(const double* pars, int W, int P, const double* x, const double* 
     Ws ws = carve(wsp, W, 1);
     if (!wsp || ws_bytes < ws.total) return LFG_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SetupArgs S{pars, W, P, 1, P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                ws.geo, ws.status, ws.prior, ws.bstatus, 0, nullptr, nullptr};
+    const SetupArgs S = setup_args_flat(pars, W, P, ws);
     const int kind = pair_kind(0, nsub, N, 0);
     const bool pair = kind > 0;
     int rc = run_front(S, ws, st, nullptr, !pair);
     if (rc) return rc;
-    LikeArgs L{ws.geo, ws.status, ws.ab, ws.donor, ws.wts, 1, nullptr, N, x, y, ye, w,
-               nsub, nullptr, nullptr, lnlike, W, nullptr, nullptr, nullptr, false, nullptr,
-               nullptr, nullptr, nullptr, 0, 0, 0ull, 0ull, nullptr};
-    L.bstatus = ws.bstatus;
-    PairArgs A{L, ElemSpec{}, nullptr, nullptr, 64, 0, 0ull, 0ull, 0, 0, 0, pair_prio(W)};
+    LikeArgs L = like_args_flat(ws, W, x, w, N, nsub);
+    L.y = y;
+    L.ye = ye;
+    L.lle = lnlike;
+    PairArgs A = pair_args(L, ElemSpec{}, 0, W);
     fill_hot(A);
     if (kind == 2) launch_pair_split(PAIR_SPLIT_LONG, unsigned(W), st, A);
     else if (pair) hipLaunchKernelGGL(k_pair<false>, dim3(W), dim3(LIKE_THREADS), 0, st, A);
@@ -5474,6 +5525,222 @@ static int apply_verdicts(double* pos, double* lnp, int W, int ndim, int half, d
     return launch_ok();
 }
 
+// k_setup's arguments for W walkers of a tree; gp: with the tree's GP
+// hyper-parameter gather (lfg_lnprior leaves it out); prop (nullable): the
+// walkers are formed inline as the stretch-move proposals of prop
+static SetupArgs setup_args_tree(const double* walkers, int W, const lfg_tree* T, const Ws& ws, bool gp,
+                                 const Propose* prop)
+{
+    SetupArgs S{};
+    S.walkers = walkers;
+    S.W = W;
+    S.ndim = T->ndim;
+    S.E = T->E;
+    S.P = 18;
+    S.gather = T->gather;
+    S.npars = T->npars;
+    S.consts = T->consts;
+    S.prior_type = T->prior_type;
+    S.prior_p1 = T->prior_p1;
+    S.prior_p2 = T->prior_p2;
+    S.prior_norm = T->prior_norm;
+    S.roche_priors = T->roche_priors;
+    S.geo = ws.geo;
+    S.status = ws.status;
+    S.prior = ws.prior;
+    S.bstatus = ws.bstatus;
+    if (gp) {
+        S.gp = T->gp;
+        S.gp_gather = T->gp_gather;
+        S.gp_base = T->gp_base;
+    }
+    S.fixed_invalid = T->fixed_invalid;
+    S.prior_c = T->prior_c;
+    if (prop) {
+        S.pos = prop->pos;
+        S.a = prop->a;
+        S.seed = prop->seed;
+        S.step = prop->step;
+        S.half = prop->half;
+        S.qout = prop->q;
+        S.zfout = prop->zfac;
+        S.lo = prop->lo;
+        S.ns = prop->ns;
+    }
+    return S;
+}
+
+// the likelihood kernels' arguments for W walkers of a tree: ln_like per
+// pair into lle, ln_prob into lnp (nullable), the fused acceptance of acc
+// (nullable) with the walkers as its proposals
+static LikeArgs like_args_tree(const Ws& ws, int W, const lfg_tree* T, double* lle, double* lnp, const double* walkers,
+                               const Accept* acc)
+{
+    LikeArgs L{};
+    L.geo = ws.geo;
+    L.status = ws.status;
+    L.AB = ws.ab;
+    L.DON = ws.donor;
+    L.WT = ws.wts;
+    L.E = T->E;
+    L.off = T->off;
+    L.N = T->max_n;
+    L.x = T->x;
+    L.y = T->y;
+    L.ye = T->ye;
+    L.w = T->w;
+    L.nsub = T->nsub;
+    L.lle = lle;
+    L.npairs = W * T->E;
+    L.prior = ws.prior;
+    L.lnp = lnp;
+    L.combine = T->E == 1;  // E > 1: k_combine_walkers after the likelihood kernels
+    L.qprop = walkers;
+    L.ndim = T->ndim;
+    if (acc) {
+        L.pos = acc->pos;
+        L.lnp_ens = acc->lnp;
+        L.zfac = acc->zfac;
+        L.half = acc->half;
+        L.seed = acc->seed;
+        L.step = acc->step;
+        L.naccept = acc->naccept;
+    }
+    if (T->gp) {  // the residuals and transitions k_gp_like filters
+        L.gp_ecl = T->gp_ecl;
+        L.res = ws.res;
+        L.gpx = ws.gpx;
+        L.gpb = ws.gpb;
+    }
+    L.bstatus = ws.bstatus;
+    return L;
+}
+
+// the workspace's snapshot of the rows of one half of the ensemble
+static double* snap_rows(const Ws& ws, int which_half, int ndim)
+{
+    return ws.snap + size_t(which_half) * ws.accstride * ndim;
+}
+
+// take it: copy the ns rows of that half of pos ([2 ns][ndim]) on the stream
+static bool snapshot_half(const Ws& ws, const double* pos, int which_half, int ns, int ndim, hipStream_t st)
+{
+    const size_t rows = size_t(ns) * ndim;
+    return hipMemcpyAsync(snap_rows(ws, which_half, ndim), pos + size_t(which_half) * rows, rows * sizeof(double),
+                          hipMemcpyDeviceToDevice, st) == hipSuccess;
+}
+
+// k_elements' / k_pair's side jobs of the speculative setup (sp nullable:
+// none): sp->in selects this half's candidates from the workspace, sp->out
+// forms the next half's from copies of S; fold_fv (nullable): the pending
+// verdicts a fold k_pair launch applies, which the next half's rows follow
+static ElemSpec spec_args(const Ws& ws, const SetupArgs& S, int W, const lfg_tree* T, const Propose* prop,
+                          const SpecCtl* sp, const double* fold_fv)
+{
+    const int npairs = W * T->E;
+    ElemSpec X{};
+    X.E = T->E;
+    X.ndim = T->ndim;
+    X.lprior = ws.prior;
+    if (!sp) return X;
+    const int h = prop->half, hn = 1 - prop->half;
+    const size_t P48 = size_t(npairs) * LFG_NGEO;
+    if (sp->in) {
+        X.jk = ws.jk + size_t(h) * W;
+        X.accflag = ws.accflag + size_t(hn) * ws.accstride;  // the partner half's acceptances
+        X.geoC = ws.geoC + 2 * h * P48;
+        X.statusC = ws.statusC + 2 * h * size_t(npairs);
+        X.bstatusC = ws.bstatusC + 2 * h * size_t(npairs);
+        X.priorC = ws.priorC + 2 * h * size_t(W);
+        X.qC = ws.qC + 2 * h * size_t(W) * T->ndim;
+        X.zfC = ws.zfC + 2 * h * size_t(W);
+        X.prior = ws.prior;
+        X.q = prop->q;
+        X.zf = prop->zfac;
+        X.bstatus = ws.bstatus;
+    }
+    if (sp->out) {
+        for (int c = 0; c < 2; ++c) {
+            SetupArgs& N = X.S[c];
+            N = S;
+            const size_t k = size_t(2 * hn + c);
+            N.half = hn;
+            N.step = hn == 0 ? prop->step + 1 : prop->step;
+            N.step_prev = prop->step;
+            N.cand = c;
+            N.geo = ws.geoC + k * P48;
+            N.status = ws.statusC + k * npairs;
+            N.bstatus = ws.bstatusC + k * npairs;
+            N.prior = ws.priorC + k * W;
+            N.qout = ws.qC + k * size_t(W) * T->ndim;
+            N.zfout = ws.zfC + k * W;
+            N.jkout = ws.jk + size_t(hn) * W;
+            if (fold_fv) {  // the next half's rows as the pending verdicts leave them
+                N.fv = fold_fv;
+                N.fsnap = snap_rows(ws, hn, T->ndim);
+                N.fstep = N.step - 1;
+            }
+        }
+        X.nspec = 2 * npairs + W;
+        X.nspecblk = (2 * ((X.nspec + ELEM_BLOCK - 1) / ELEM_BLOCK) + 7) / 8 * 8;  // keeps the pair -> XCD map
+    }
+    return X;
+}
+
+// PairArgs' proposal fields (prop nullable: the partner draw of the candidate
+// choice) and fold fields (fold nullable: the deferred acceptance inside
+// k_pair, applying the pending verdicts fv of step fstep)
+static void pair_args_move(PairArgs& A, const Ws& ws, int ndim, const Propose* prop, const FoldCtl* fold,
+                           const double* fv, unsigned long long fstep)
+{
+    if (prop) {
+        A.jseed = prop->seed;
+        A.jstep = prop->step;
+        A.jhalf = prop->half;
+        A.jlo = prop->lo;
+        A.jns = prop->ns;
+    }
+    if (fold) {
+        A.fv = fv;
+        A.vout = fold->vout;
+        A.fpos = fold->pos;
+        A.flnp = fold->lnp;
+        A.fnacc = fold->naccept;
+        A.fsnap = snap_rows(ws, prop->half, ndim);
+        A.fstep = fstep;
+        A.fa = prop->a;
+        A.L.seed = prop->seed;
+        A.L.step = prop->step;
+        A.L.half = prop->half;
+        A.L.zfac = prop->zfac;
+    }
+}
+
+// what follows the likelihood kernel(s) of either layout: the GP filter of a
+// GP tree, ln_prob of walkers of E > 1 eclipses, the shard's verdicts from
+// its ln_prob (fold nullable: not folding, or k_pair formed them), event 3.
+// prop is read only with fold, which needs one (lnprob_impl's validation)
+static int launch_tail(const LikeArgs& L, int W, const lfg_tree* T, double* lnp, const Propose* prop,
+                       const FoldCtl* fold, hipStream_t st, void* const* ev)
+{
+    int rc;
+    if (T->gp) {
+        hipLaunchKernelGGL(k_gp_like, dim3(T->E * ((W + GP_PAIRS - 1) / GP_PAIRS)), dim3(GP_BLOCK), 0, st, L);
+        if ((rc = launch_ok())) return rc;
+    }
+    if (T->E > 1) {
+        hipLaunchKernelGGL(k_combine_walkers, dim3((W + 3) / 4), dim3(256), 0, st, L);
+        if ((rc = launch_ok())) return rc;
+    }
+    if (fold) {
+        hipLaunchKernelGGL(k_verdict, dim3((W + 63) / 64), dim3(64), 0, st, lnp, fold->lnp, prop->zfac, W, prop->lo,
+                           prop->ns, prop->half, prop->seed, prop->step, fold->vout);
+        if (launch_ok()) return LFG_E_LAUNCH;
+    }
+    mark_event(ev, 3, st);
+    return LFG_OK;
+}
+
 static int lnprob_impl(const double* walkers, int W, const lfg_tree* T, double* lnp, double* lnlike_e, void* wsp,
                        size_t ws_bytes, void* stream, void* const* ev, const Accept* acc = nullptr,
                        const Propose* prop = nullptr, const SpecCtl* sp = nullptr, const FoldCtl* fold = nullptr)
@@ -5502,211 +5769,63 @@ static int lnprob_impl(const double* walkers, int W, const lfg_tree* T, double* 
         if (rc) return rc;
         fv = nullptr;
     }
-    auto mark = [&](int i) {
-        if (ev && ev[i]) (void)hipEventRecord(static_cast<hipEvent_t>(ev[i]), st);
-    };
-    SetupArgs S{walkers, W, T->ndim, T->E, 18, T->gather, T->npars, T->consts, T->prior_type, T->prior_p1,
-                T->prior_p2, T->prior_norm, T->roche_priors, ws.geo, ws.status, ws.prior, ws.bstatus, T->gp,
-                T->gp_gather, T->gp_base};
-    S.fixed_invalid = T->fixed_invalid;
-    S.prior_c = T->prior_c;
-    if (prop) {
-        S.pos = prop->pos;
-        S.a = prop->a;
-        S.seed = prop->seed;
-        S.step = prop->step;
-        S.half = prop->half;
-        S.qout = prop->q;
-        S.zfout = prop->zfac;
-        S.lo = prop->lo;
-        S.ns = prop->ns;
-    }
-    const int npairs = W * T->E;
-    ElemSpec X{};
-    X.E = T->E;
-    X.ndim = T->ndim;
-    X.lprior = ws.prior;
-    if (sp) {
-        const int h = prop->half, hn = 1 - prop->half;
-        const size_t P48 = size_t(npairs) * LFG_NGEO;
-        if (sp->in) {
-            X.jk = ws.jk + size_t(h) * W;
-            X.accflag = ws.accflag + size_t(hn) * ws.accstride;  // the partner half's acceptances
-            X.geoC = ws.geoC + 2 * h * P48;
-            X.statusC = ws.statusC + 2 * h * size_t(npairs);
-            X.bstatusC = ws.bstatusC + 2 * h * size_t(npairs);
-            X.priorC = ws.priorC + 2 * h * size_t(W);
-            X.qC = ws.qC + 2 * h * size_t(W) * T->ndim;
-            X.zfC = ws.zfC + 2 * h * size_t(W);
-            X.prior = ws.prior;
-            X.q = prop->q;
-            X.zf = prop->zfac;
-            X.bstatus = ws.bstatus;
-        }
-        if (sp->out) {
-            for (int c = 0; c < 2; ++c) {
-                SetupArgs& N = X.S[c];
-                N = S;
-                const size_t k = size_t(2 * hn + c);
-                N.half = hn;
-                N.step = hn == 0 ? prop->step + 1 : prop->step;
-                N.step_prev = prop->step;
-                N.cand = c;
-                N.geo = ws.geoC + k * P48;
-                N.status = ws.statusC + k * npairs;
-                N.bstatus = ws.bstatusC + k * npairs;
-                N.prior = ws.priorC + k * W;
-                N.qout = ws.qC + k * size_t(W) * T->ndim;
-                N.zfout = ws.zfC + k * W;
-                N.jkout = ws.jk + size_t(hn) * W;
-                if (fold_pair && fv) {  // the next half's rows as the pending verdicts leave them
-                    N.fv = fv;
-                    N.fsnap = ws.snap + size_t(hn) * ws.accstride * T->ndim;
-                    N.fstep = N.step - 1;
-                }
-            }
-            X.nspec = 2 * npairs + W;
-            X.nspecblk = (2 * ((X.nspec + ELEM_BLOCK - 1) / ELEM_BLOCK) + 7) / 8 * 8;  // keeps the pair -> XCD map
-        }
-    }
+    const SetupArgs S = setup_args_tree(walkers, W, T, ws, true, prop);
+    const ElemSpec X = spec_args(ws, S, W, T, prop, sp, fold_pair ? fv : nullptr);
     // k_pair: the element solve and the likelihood of a pair in one
     // workgroup (one-tile eclipses, S = 1; GP trees through k_pair<true> and
     // k_gp_like).  The speculative lanes fill whole waves: wave 0 of blocks
     // [0, 2 nbc), nbc blocks per candidate, so there must be 2 nbc pairs
-    const int spl = 64, nbc = (X.nspec + 63) / 64;
+    const int npairs = W * T->E, nbc = (X.nspec + 63) / 64;
     const bool pair_path = kind > 0 && (X.nspec == 0 || 2 * nbc <= npairs);
     if (fold_pair && !pair_path) return LFG_E_ARGS;  // (fold_pair's test is pair_path's)
-    // the end of every path but the fold's own: the shard's verdicts from its
-    // ln_prob (fold fallback), then the last event
-    auto finish = [&]() {
-        if (fold) {
-            hipLaunchKernelGGL(k_verdict, dim3((W + 63) / 64), dim3(64), 0, st, lnp, fold->lnp, prop->zfac, W,
-                               prop->lo, prop->ns, prop->half, prop->seed, prop->step, fold->vout);
-            if (launch_ok()) return LFG_E_LAUNCH;
-        }
-        mark(3);
-        return LFG_OK;
-    };
     int rc = run_front(S, ws, st, ev, !pair_path, &X, !(sp && sp->in));
     if (rc) return rc;
-    double* lle = lnlike_e ? lnlike_e : ws.lle;
-    LikeArgs L{ws.geo, ws.status, ws.ab, ws.donor, ws.wts, T->E, T->off, T->max_n, T->x, T->y, T->ye,
-               T->w, T->nsub, nullptr, nullptr, lle, npairs, T->gp ? T->gp_ecl : nullptr, ws.prior, lnp,
-               true, acc ? acc->pos : nullptr, acc ? acc->lnp : nullptr, walkers, acc ? acc->zfac : nullptr,
-               T->ndim, acc ? acc->half : 0, acc ? acc->seed : 0ull, acc ? acc->step : 0ull,
-               acc ? acc->naccept : nullptr};
-    L.bstatus = ws.bstatus;
+    LikeArgs L = like_args_tree(ws, W, T, lnlike_e ? lnlike_e : ws.lle, lnp, walkers, acc);
     // sharded: k_accept_regen records them
     L.accflag = (sp && acc) ? ws.accflag + size_t(prop->half) * ws.accstride : nullptr;
-    L.combine = T->E == 1;  // E > 1: k_combine_walkers after the likelihood kernels
+    // the speculative lanes of a k_pair launch read partner rows from the
+    // workspace's snapshots; on the two-kernel layout a k_pair-eligible tree
+    // leaves the snapshot a k_pair launch would have left, so that a layout
+    // switch (lfg_set_layout) before the chain's next half reads valid rows
+    const bool snaps = sp && sp->out && T->E == 1 && (pair_path || pair_eligible(T->gp, T->nsub, T->max_n, T->ndim));
     if (pair_path) {
-        PairArgs A{L, X, nullptr, nullptr, spl, nbc, 0ull, 0ull, 0, 0, 0, pair_prio(npairs)};
-        if (prop) {
-            A.jseed = prop->seed;
-            A.jstep = prop->step;
-            A.jhalf = prop->half;
-            A.jlo = prop->lo;
-            A.jns = prop->ns;
-        }
-        if (fold_pair) {
-            const int h = prop->half;
-            A.fv = fv;
-            A.vout = fold->vout;
-            A.fpos = fold->pos;
-            A.flnp = fold->lnp;
-            A.fnacc = fold->naccept;
-            A.fsnap = ws.snap + size_t(h) * ws.accstride * T->ndim;
-            A.fstep = fstep;
-            A.fa = prop->a;
-            A.L.seed = prop->seed;
-            A.L.step = prop->step;
-            A.L.half = h;
-            A.L.zfac = prop->zfac;
-            fill_hot(A);
-            launch_pair_split(kind == 2 ? PAIR_SPLIT_FOLD_LONG : PAIR_SPLIT_FOLD, unsigned(npairs), st, A);
-            if ((rc = launch_ok())) return rc;
-            mark(3);
-            return LFG_OK;
-        }
-        if (sp && sp->out && acc && T->E == 1) {
+        PairArgs A = pair_args(L, X, nbc, npairs);
+        pair_args_move(A, ws, T->ndim, prop, fold_pair ? fold : nullptr, fv, fstep);
+        if (snaps && acc) {
             // this launch accepts moves of half h while its speculative lanes
             // read half h's rows: they read the snapshot of them instead (taken
             // by the launch before, or here), and the launch snapshots half 1 - h
-            const int h = prop->half, hn = 1 - h, ns = prop->ns;
-            const size_t rows = size_t(ns) * T->ndim;
-            double* snap_h = ws.snap + size_t(h) * ws.accstride * T->ndim;
-            if (!sp->in && hipMemcpyAsync(snap_h, prop->pos + size_t(h) * rows, rows * sizeof(double),
-                                          hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return LFG_E_LAUNCH;
-            A.X.S[0].ppos = A.X.S[1].ppos = snap_h;
-            A.snap_src = prop->pos + size_t(hn) * rows;
-            A.snap_dst = ws.snap + size_t(hn) * ws.accstride * T->ndim;
+            const int h = prop->half, hn = 1 - h;
+            if (!sp->in && !snapshot_half(ws, prop->pos, h, prop->ns, T->ndim, st)) return LFG_E_LAUNCH;
+            A.X.S[0].ppos = A.X.S[1].ppos = snap_rows(ws, h, T->ndim);
+            A.snap_src = prop->pos + size_t(hn) * prop->ns * T->ndim;
+            A.snap_dst = snap_rows(ws, hn, T->ndim);
         }
-        if (T->gp) {
-            L.res = ws.res;
-            L.gpx = ws.gpx;
-            L.gpb = ws.gpb;
-            A.L = L;
-            fill_hot(A);
-            hipLaunchKernelGGL(k_pair<true>, dim3(npairs), dim3(LIKE_THREADS), 0, st, A);
-            if ((rc = launch_ok())) return rc;
-            hipLaunchKernelGGL(k_gp_like, dim3(T->E * ((W + GP_PAIRS - 1) / GP_PAIRS)), dim3(GP_BLOCK), 0, st, L);
-        } else if (kind == 2) {
-            fill_hot(A);
-            launch_pair_split(PAIR_SPLIT_LONG, unsigned(npairs), st, A);
-        } else {
-            fill_hot(A);
-            hipLaunchKernelGGL(k_pair<false>, dim3(npairs), dim3(LIKE_THREADS), 0, st, A);
-        }
-        if ((rc = launch_ok())) return rc;
-        if (T->E > 1) {
-            hipLaunchKernelGGL(k_combine_walkers, dim3((W + 3) / 4), dim3(256), 0, st, L);
-            if ((rc = launch_ok())) return rc;
-        }
-        return finish();
-    }
-    if (sp && sp->out && acc && T->E == 1 && pair_eligible(T->gp, T->nsub, T->max_n, T->ndim)) {
-        // a k_pair-eligible tree on the two-kernel layout (lfg_set_layout(0)):
-        // leave the partner-half snapshot a k_pair launch would have left, so
-        // that a layout switch before the chain's next half reads valid rows
-        const int hn = 1 - prop->half;
-        const size_t rows = size_t(prop->ns) * T->ndim;
-        if (hipMemcpyAsync(ws.snap + size_t(hn) * ws.accstride * T->ndim, prop->pos + size_t(hn) * rows,
-                           rows * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return LFG_E_LAUNCH;
-    }
-    if (sp && sp->out && fold && T->E == 1 && pair_eligible(T->gp, T->nsub, T->max_n, T->ndim)) {
-        // the deferred acceptance on the two-kernel layout: a fold k_pair
-        // launch snapshots its own half's rows (final until its verdicts are
-        // applied) for the next launch's speculative lanes; leave the same
-        // snapshot, so that a layout switch before the next half reads it valid
-        const int h = prop->half;
-        const size_t rows = size_t(prop->ns) * T->ndim;
-        if (hipMemcpyAsync(ws.snap + size_t(h) * ws.accstride * T->ndim, prop->pos + size_t(h) * rows,
-                           rows * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return LFG_E_LAUNCH;
-    }
-    if (T->gp) {
-        L.res = ws.res;
-        L.gpx = ws.gpx;
-        L.gpb = ws.gpb;
-        hipLaunchKernelGGL(k_gp_dcp, dim3((npairs + 64 / DCP_LANES - 1) / (64 / DCP_LANES)), dim3(64), 0, st, ws.geo,
-                           ws.status, npairs);
-        if ((rc = launch_ok())) return rc;
-        if (T->nsub > 1) hipLaunchKernelGGL((k_lnlike<2, true>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
-        else hipLaunchKernelGGL((k_lnlike<2, false>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
-        if ((rc = launch_ok())) return rc;
-        hipLaunchKernelGGL(k_gp_like, dim3(T->E * ((W + GP_PAIRS - 1) / GP_PAIRS)), dim3(GP_BLOCK), 0, st, L);
+        fill_hot(A);
+        if (fold_pair) launch_pair_split(kind == 2 ? PAIR_SPLIT_FOLD_LONG : PAIR_SPLIT_FOLD, unsigned(npairs), st, A);
+        else if (T->gp) hipLaunchKernelGGL(k_pair<true>, dim3(npairs), dim3(LIKE_THREADS), 0, st, A);
+        else if (kind == 2) launch_pair_split(PAIR_SPLIT_LONG, unsigned(npairs), st, A);
+        else hipLaunchKernelGGL(k_pair<false>, dim3(npairs), dim3(LIKE_THREADS), 0, st, A);
     } else {
-        if (T->nsub > 1) hipLaunchKernelGGL((k_lnlike<1, true>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
-        else hipLaunchKernelGGL((k_lnlike<1, false>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
+        // the partner half's rows, as the fused acceptance's k_pair leaves them
+        if (snaps && acc && !snapshot_half(ws, prop->pos, 1 - prop->half, prop->ns, T->ndim, st)) return LFG_E_LAUNCH;
+        // the deferred acceptance: a fold k_pair launch snapshots its own
+        // half's rows (final until its verdicts are applied) for the next
+        // launch's speculative lanes
+        if (snaps && fold && !snapshot_half(ws, prop->pos, prop->half, prop->ns, T->ndim, st)) return LFG_E_LAUNCH;
+        if (T->gp) {
+            hipLaunchKernelGGL(k_gp_dcp, dim3((npairs + 64 / DCP_LANES - 1) / (64 / DCP_LANES)), dim3(64), 0, st, ws.geo,
+                               ws.status, npairs);
+            if ((rc = launch_ok())) return rc;
+            if (T->nsub > 1) hipLaunchKernelGGL((k_lnlike<2, true>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
+            else hipLaunchKernelGGL((k_lnlike<2, false>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
+        } else {
+            if (T->nsub > 1) hipLaunchKernelGGL((k_lnlike<1, true>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
+            else hipLaunchKernelGGL((k_lnlike<1, false>), dim3(npairs), dim3(LIKE_THREADS), 0, st, L);
+        }
     }
     if ((rc = launch_ok())) return rc;
-    if (T->E > 1) {
-        hipLaunchKernelGGL(k_combine_walkers, dim3((W + 3) / 4), dim3(256), 0, st, L);
-        if ((rc = launch_ok())) return rc;
-    }
-    return finish();
+    return launch_tail(L, W, T, lnp, prop, fold_pair ? nullptr : fold, st, ev);
 }
 
 int lfg_lnprior(const double* walkers, int W, const lfg_tree* T, double* lnprior, void* wsp, size_t ws_bytes,
@@ -5716,11 +5835,7 @@ int lfg_lnprior(const double* walkers, int W, const lfg_tree* T, double* lnprior
     Ws ws = carve(wsp, W, T->E);
     if (!wsp || ws_bytes < ws.total) return LFG_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SetupArgs S{walkers, W, T->ndim, T->E, 18, T->gather, T->npars, T->consts, T->prior_type, T->prior_p1,
-                T->prior_p2, T->prior_norm, T->roche_priors, ws.geo, ws.status, ws.prior, ws.bstatus, 0,
-                nullptr, nullptr};
-    S.fixed_invalid = T->fixed_invalid;
-    S.prior_c = T->prior_c;
+    const SetupArgs S = setup_args_tree(walkers, W, T, ws, false, nullptr);
     const int nlanes = 2 * W * T->E + W;
     hipLaunchKernelGGL(k_setup, dim3((nlanes + SETUP_BLOCK - 1) / SETUP_BLOCK), dim3(SETUP_BLOCK), 0, st, S);
     int rc = launch_ok();
@@ -5763,7 +5878,6 @@ int lfg_stretch_step_half_spec(double* pos, double* lnp, int W, int half, double
     const Accept acc{pos, lnp, zfac, half, seed, step, naccept};
     const Propose prop{pos, a, q, zfac, half, seed, step, 0, W / 2};
     const SpecCtl sp{spec_in != 0, spec_out != 0};
-    // the fused-element build has no k_elements to host the candidates: plain half-step
     return lnprob_impl(q, W / 2, T, lnp_new, nullptr, wsp, ws_bytes, stream, ev, &acc, &prop, &sp);
 }
 
@@ -5934,8 +6048,7 @@ int lfg_elements(const double* pars, int W, int P, double* a, double* b, double*
     Ws ws = carve(wsp, W, 1);
     if (!wsp || ws_bytes < ws.total) return LFG_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SetupArgs S{pars, W, P, 1, P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                ws.geo, ws.status, ws.prior, ws.bstatus, 0, nullptr, nullptr};
+    const SetupArgs S = setup_args_flat(pars, W, P, ws);
     int rc = run_front(S, ws, st, nullptr, true);  // the white-box tables come from k_elements
     if (rc) return rc;
     if (a || b || wgt || donor) {

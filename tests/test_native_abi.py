@@ -167,6 +167,46 @@ def test_stale_library_is_rebuilt(tmp_path, monkeypatch):
     assert len(calls) == 2
 
 
+def test_source_hash_covers_every_included_header(tmp_path, monkeypatch):
+    """Whatever a unit can include is hashed: every #include "..." under
+    csrc/ resolves to a file source_hash() reads, and one changed byte in any
+    of those headers changes the hash (so verify() refuses a library built
+    before the change)."""
+    import shutil
+    csrc = os.path.join(ROOT, "lfit_python_amd", "csrc")
+    hashed = set(map(os.path.realpath, _native.SOURCES + [_native.SPLIT_SOURCE] + _native.HEADERS))
+    included = set()
+    for name in sorted(os.listdir(csrc)):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, name)).read(), flags=re.M):
+            found = [p for p in (os.path.join(csrc, inc), os.path.join(_native.INCLUDE, inc)) if os.path.isfile(p)]
+            assert found, "%s includes %s, which is neither in csrc/ nor in include/" % (name, inc)
+            assert os.path.realpath(found[0]) in hashed, "%s includes %s, which source_hash() does not read" % (name, inc)
+            included.add(os.path.realpath(found[0]))
+    headers = sorted(p for p in included if not p.endswith(".hip"))
+    assert len(headers) >= 5 and os.path.realpath(os.path.join(csrc, "lfg_philox.hpp")) in headers
+
+    def copied(p):
+        return os.path.join(str(tmp_path), os.path.relpath(os.path.realpath(p), os.path.realpath(ROOT)))
+    for p in hashed:
+        os.makedirs(os.path.dirname(copied(p)), exist_ok=True)
+        shutil.copy(p, copied(p))
+    want = _native.source_hash()
+    monkeypatch.setattr(_native, "REPO", str(tmp_path))
+    monkeypatch.setattr(_native, "SOURCES", [copied(p) for p in _native.SOURCES])
+    monkeypatch.setattr(_native, "SPLIT_SOURCE", copied(_native.SPLIT_SOURCE))
+    monkeypatch.setattr(_native, "HEADERS", [copied(p) for p in _native.HEADERS])
+    assert _native.source_hash() == want          # the copy is the tree
+    for h in headers:
+        data = open(copied(h), "rb").read()
+        k = len(data) // 2
+        with open(copied(h), "wb") as fh:
+            fh.write(data[:k] + bytes([data[k] ^ 1]) + data[k + 1:])
+        assert _native.source_hash() != want, h
+        with open(copied(h), "wb") as fh:
+            fh.write(data)
+    assert _native.source_hash() == want
+
+
 def test_foreign_library_refused(tmp_path):
     """LFG_LIB without LFG_DIAGNOSTIC=1 is refused at import; with it, a
     library carrying another source hash fails verify() (what smoke() and the
