@@ -160,7 +160,9 @@ def gp_lnlike_segments(x, r, ye, ampin, ampout, tau, blocks, K=4):
     ll = 0.0
     mu, Sig = np.zeros(4), pinf.copy()
     for s, (A, c, Pend, J, eta, kap, ns) in enumerate(elems):
-        if s > 0:
+        if ns == 0:  # an empty segment (n < K): nothing observed, no transition
+            continue
+        if bounds[s] > 0:  # the gap from the last point before it (none into the first point)
             i = bounds[s]
             F = trans(x[i] - x[i - 1])
             mu = F @ mu

@@ -161,6 +161,18 @@ def test_gp_kalman_matches_dense_oracle(oracle):
         for K in (1, 3, 8):  # k_gp_like's parallel-in-time form (8 segments), empty segments included
             seg = gp_lnlike_segments(x, r, ye, a1, a2, tau, blocks, K)
             assert abs(dense - seg) <= 1e-10 * max(1.0, abs(dense)), (trial, K, dense, seg)
+    # fewer points than segments (the seeded n above are 48 .. 117): an
+    # empty segment is skipped and no gap is taken into the first point, with
+    # the first point in a block, in none, and a block that opens on a later one
+    for n in range(1, 10):
+        x = np.sort(rng.uniform(-0.2, 0.3, n))
+        r = 0.004 * rng.standard_normal(n)
+        ye = rng.uniform(0.002, 0.008, n)
+        a1, a2, tau = np.exp(rng.uniform(-12, -7)), np.exp(rng.uniform(-12, -7)), np.exp(rng.uniform(-6.9, -2))
+        for blocks in ([(-0.98, -0.03), (0.02, 0.97)], [], [(x[0], x[0])], [(x[-1], 0.97)], [(-0.98, x[n // 2])]):
+            dense = oracle.gp_lnlike(x, r, ye, a1, a2, tau, blocks)
+            seg = gp_lnlike_segments(x, r, ye, a1, a2, tau, blocks, 8)
+            assert abs(dense - seg) <= 1e-10 * max(1.0, abs(dense)), (n, blocks, dense, seg)
 
 
 def test_oracle_gp_lnprob_matches_reference(oracle):

@@ -479,23 +479,51 @@ def test_wdphases_matches_oracle(oracle):
         assert got[0] < dphi / 2 < got[1]
 
 
-def test_gp_kernel_matches_dense_oracle(oracle):
+# (n, W, nb); None: the shape the test has always had.  The others: one and two
+# points, fewer points than a wave has lanes, more sets than a wave, no block
+# and three, a tied triple where n >= 9
+GP_KERNEL_SHAPES = [None, (1, 1, 2), (2, 3, 2), (7, 65, 0), (9, 2, 3), (64, 5, 2)]
+
+
+@pytest.mark.parametrize("shape", GP_KERNEL_SHAPES, ids=lambda s: "n300_W24" if s is None else "n%d_W%d_nb%d" % s)
+def test_gp_kernel_matches_dense_oracle(oracle, shape):
     """lfg_gp_lnlike (Kalman filter, one wave per set) against the dense
     Cholesky oracle; bar 1e-9 relative (both exact, FP64 rounding apart)."""
     from lfit_python_amd import gp
     rng = np.random.default_rng(3)
-    n, W = 300, 24
-    x = rng.permutation(np.linspace(-0.2, 0.3, n))   # unsorted input: the wrapper sorts
-    ye = rng.uniform(0.003, 0.006, n)
-    res = 0.004 * rng.standard_normal((W, n))
-    hyp = np.stack([np.exp(rng.uniform(-11, -8, W)), np.exp(rng.uniform(-11, -8, W)),
-                    np.exp(rng.uniform(-6.9, -2, W))], axis=1)
-    d = rng.uniform(0.01, 0.05, W)
-    blocks = np.stack([np.stack([-1 + d, -d], 1), np.stack([d, 1 - d], 1)], axis=1)
+    if shape is None:
+        n, W = 300, 24
+        x = rng.permutation(np.linspace(-0.2, 0.3, n))   # unsorted input: the wrapper sorts
+        ye = rng.uniform(0.003, 0.006, n)
+        res = 0.004 * rng.standard_normal((W, n))
+        hyp = np.stack([np.exp(rng.uniform(-11, -8, W)), np.exp(rng.uniform(-11, -8, W)),
+                        np.exp(rng.uniform(-6.9, -2, W))], axis=1)
+        d = rng.uniform(0.01, 0.05, W)
+        blocks = np.stack([np.stack([-1 + d, -d], 1), np.stack([d, 1 - d], 1)], axis=1)
+    else:
+        # hyper-parameters from the whole range the tree tests use
+        # (tests/gp_trees.py says what the 1e-9 bar rests on there)
+        from tests.gp_trees import LN_AMP, LN_TAU
+        n, W, nb = shape
+        rng = np.random.default_rng(1000 * n + W)
+        x = np.sort(rng.uniform(-0.2, 0.3, n))
+        if n >= 9:
+            x[4:7] = x[4]                                # a tied triple: d = 0
+        x = rng.permutation(x)
+        ye = rng.uniform(0.003, 0.006, n)
+        res = 0.004 * rng.standard_normal((W, n))
+        hyp = np.exp(np.stack([rng.uniform(*LN_AMP, W), rng.uniform(*LN_AMP, W), rng.uniform(*LN_TAU, W)], axis=1))
+        d = rng.uniform(0.01, 0.05, W)
+        blocks = np.stack([np.stack([-1 + d, -d], 1), np.stack([d, 1 - d], 1),
+                           np.stack([-d / 2, d / 2], 1)], axis=1)[:, :nb]
     got = gp.log_likelihood_batch(x, ye, res, hyp, blocks)
+    assert got.shape == (W,)
+    worst = 0.0
     for i in range(W):
         ref = oracle.gp_lnlike(x, res[i], ye, *hyp[i], blocks[i])
+        worst = max(worst, abs(got[i] - ref) / abs(ref))
         assert abs(got[i] - ref) <= 1e-9 * abs(ref), (i, got[i], ref)
+    print("k_gp %s: largest relative error %.2e" % (shape, worst))
 
 
 @LAYOUTS
