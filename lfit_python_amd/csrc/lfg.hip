@@ -1501,6 +1501,47 @@ __device__ __forceinline__ void block_scan(unsigned long long (*acc)[LIKE_TILE +
     }
 }
 
+// k_pair's one-tile likelihood phase (LFG_PAIR_RUNSCAN, default on;
+// -DLFG_PAIR_RUNSCAN=0 compiles block_scan<6> by all eight waves, every wave
+// running the whole phase, as before).  A config-2 eclipse has 300 points in a
+// tile of 512: block_scan<6> cost each of the 8 waves six 6-step 64-bit DPP
+// scans and six cross-wave scans for about 1 800 prefix sums in all, and the
+// waves above the last point ran the conversions, sincospi, the flux and the
+// quotient for nothing.  With the switch on a wave scans one array (run_scan)
+// and a wave without a point only reaches the barriers.
+#ifndef LFG_PAIR_RUNSCAN
+#define LFG_PAIR_RUNSCAN 1
+#endif
+
+// inclusive prefix of one difference array over [0, m), in place, by one
+// wave (all 64 lanes call it): lane l owns the run [l R, min((l + 1) R, m)),
+// R = ceil(m / 64) <= RUN_MAX; it sums its run (ext, nullable: the array's
+// second copy, summed in), one wave scan runs over the run totals, and the
+// lane writes the running prefix back (long_tables' step (f)).  The sums are
+// int64: the order changes no bit.
+constexpr int RUN_MAX = LIKE_TILE / 64;
+__device__ __forceinline__ void run_scan(unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ ext,
+                                         int m, int lane)
+{
+    const int R = (m + 63) >> 6, p0 = lane * R;
+    long long v[RUN_MAX];
+    long long own = 0;
+#pragma unroll
+    for (int k = 0; k < RUN_MAX; ++k) {
+        const int p = p0 + k;
+        const bool in = k < R && p < m;
+        v[k] = in ? static_cast<long long>(acc[p] + (ext ? ext[p] : 0ull)) : 0;
+        own += v[k];
+    }
+    long long run = wave_scan_incl(own, lane) - own;
+#pragma unroll
+    for (int k = 0; k < RUN_MAX; ++k) {
+        const int p = p0 + k;
+        run += v[k];
+        if (k < R && p < m) acc[p] = static_cast<unsigned long long>(run);
+    }
+}
+
 __device__ __forceinline__ double wrap_phase(double ph) { return ph - floor(ph + 0.5); }
 
 // sincospi out of line: inlined into the tile loop, its polynomial constants
@@ -3847,7 +3888,9 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
     } SU;
     __shared__ unsigned long long sacc[6][LIKE_TILE + 1];
     __shared__ unsigned long long stot[2];
+#if !LFG_PAIR_RUNSCAN
     __shared__ long long spart[6][LIKE_THREADS / 64];
+#endif
     __shared__ double red[LIKE_THREADS / 64];
     __shared__ int sflagw[LIKE_THREADS / 64];
     __shared__ int sflag[1];
@@ -3992,16 +4035,29 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
             LT.sgeo[tid - (nt - LFG_NGEO)] = G[tid - (nt - LFG_NGEO)];
         }
     } else {
+#if LFG_PAIR_RUNSCAN
+        // the sinks add at indices < m only (apply_runs_batched, donor, flush)
+        // and run_scan reads [0, m): the slots above m stay as they are, and
+        // a wave wholly above m stores nothing
+        if (tid <= m) {
+            for (int i = 0; i < 6; ++i) sacc[i][tid] = 0ull;
+            SU.s.X[0][tid] = 0ull;
+            SU.s.X[1][tid] = 0ull;
+        }
+#else
         for (int i = 0; i < 6; ++i) sacc[i][tid] = 0ull;
         SU.s.X[0][tid] = 0ull;
         SU.s.X[1][tid] = 0ull;
+#endif
     }
     if (tid == 0) {
+#if !LFG_PAIR_RUNSCAN  // (no sink adds at slot nt and no scan reads it)
         if constexpr (!LONG) {
             for (int i = 0; i < 6; ++i) sacc[i][nt] = 0ull;
             SU.s.X[0][nt] = 0ull;
             SU.s.X[1][nt] = 0ull;
         }
+#endif
         stot[0] = stot[1] = 0ull;
         sjob = (X.nspec > 0 && pair < 2 * A.nbc) ? 8 : 9;
     }
@@ -4447,6 +4503,70 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
         const double dn = double(static_cast<long long>(stot[1])) * (FX_INV / PAIR_DON_S);
         const double phc = own ? sph[tid] : 0.0;
         double fw = 0.0, fd = 0.0, eb = 0.0, R3 = 0.0, R4 = 0.0, R5 = 0.0;
+#if LFG_PAIR_RUNSCAN
+        // A wave whose first thread is past the last point (wave-uniform)
+        // does nothing from here on except reach the barriers; its chi^2 is 0.
+        // BARRIER INVARIANT: no __syncthreads() may sit inside an if (pw)
+        // branch.  Every wave of the workgroup reaches every barrier on every
+        // path after B1: st != ST_OK (finish_walker's, all threads call it),
+        // the scan's barrier below (dir and m are uniform over the workgroup),
+        // GP's return, the chi^2 barrier, and acc1's.  A skipped barrier hangs
+        // the workgroup.
+        const bool pw = wv * 64 < m;
+        // the terms that depend on no sum, ahead of the scan's barrier: their
+        // FP64 latency overlaps the scanning waves
+        double e0 = 0.0, e1 = 0.0, beam = 0.0;
+        if (pw) {
+            const double2 scp2 = sincospi_ool(2.0 * phc);
+            e0 = s * scp2.y;
+            e1 = -s * scp2.x;
+            const double bden = Gc[G_BDEN], fis = Gc[G_FIS];
+            if (bden > 0.0) beam = (fis + (1.0 - fis) * fmax(Gc[G_NB0] * e0 + Gc[G_NB1] * e1 + Gc[G_NB2] * c, 0.0)) / bden;
+        }
+        if (dir) {
+            if (own) {
+                const double wk = L.w ? L.w[o0 + tid] : 0.0;
+                const double2 f2 = pair_direct_wd_disc(SU.ab, ul, swt, phc, wk, twd, swt[NDISC_R]);
+                // MODEL_SPEC 3: a NaN width gives a NaN flux (such a tile is
+                // always point-major: its window fails the sortedness test)
+                fw = isnan(wk) ? NAN : f2.x;
+                fd = f2.y;
+                eb = direct_spot(sab, sbw, phc, wk, 1.0 / wspot);
+            }
+        } else {
+            // wave i < 6 scans difference array i in place (arrays 0 and 1
+            // with their second copies); after the barrier (the one block_scan
+            // has between its stages) a point's six prefixes are LDS reads
+            if (wv < 6) run_scan(sacc[wv], wv < 2 ? SU.s.X[wv] : nullptr, m, lane);
+            __syncthreads();  // every wave, on every path through this branch
+            PAIR_STAMP(12, tid == 0);
+            if (own) {
+                fw = double(static_cast<long long>(sacc[0][tid])) * FX_INV;
+                fd = double(static_cast<long long>(sacc[1][tid])) * FX_INV;
+                eb = double(static_cast<long long>(sacc[2][tid])) * (FX_INV / PAIR_SPOT_S) / wspot;
+                R3 = double(static_cast<long long>(sacc[3][tid]));
+                R4 = double(static_cast<long long>(sacc[4][tid]));
+                R5 = double(static_cast<long long>(sacc[5][tid]));
+            }
+        }
+        if (pw) {
+            double D = 0.0;
+            if (!dir) D = (e0 * R3 + e1 * R4 + c * R5) * (FX_INV / PAIR_DON_S);
+            else if (own) D = direct_donor(sdq, e0, e1, c);
+            const double sbs = beam * (1.0 - eb), srs = D / dn;
+            if (own) {
+                const double f = Gc[G_WDF] * (1.0 - fw) + Gc[G_DF] * (1.0 - fd) + Gc[G_SF] * sbs + Gc[G_RSF] * srs;
+                if (GP) {
+                    const size_t q = size_t(pair) * L.N + tid;
+                    L.res[q] = sy[tid] - f;
+                    L.gpb[q] = gp_block(L.x[o0 + tid], L.gp_ecl[2 * e], L.gp_ecl[2 * e + 1], sdcp, Gc[G_PHI0]);
+                } else {
+                    const double rr = (sy[tid] - f) / sye[tid];
+                    chi = isnan(f) ? INFINITY : rr * rr;
+                }
+            }
+        }
+#else
         if (dir) {
             if (own) {
                 const double wk = L.w ? L.w[o0 + tid] : 0.0;
@@ -4488,9 +4608,14 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
                 chi = isnan(f) ? INFINITY : rr * rr;
             }
         }
+#endif  // LFG_PAIR_RUNSCAN
     }
     if (GP) return;  // k_gp_like forms ln_like from the residuals
+#if LFG_PAIR_RUNSCAN
+    if (LONG || wv * 64 < m) chi = wave_sum(chi);  // (a wave without a point holds chi = 0)
+#else
     chi = wave_sum(chi);
+#endif
     if (lane == 0) red[wv] = chi;
     __syncthreads();
     // the finish (finish_walker's arithmetic) from the values thread 0
