@@ -24,8 +24,20 @@
 #include "lfg.h"
 #include "lfg_device.hpp"
 #include "lfg_tables.hpp"
+#include "lfg_sweep.hpp"
 
 using namespace lfg;
+
+// k_pair's sinks (LFG_PAIR_SINK_MERGE, default on; -DLFG_PAIR_SINK_MERGE=0
+// compiles the code as it was): a run end's adjacent entries are summed
+// before they go into the difference array (apply_runs_merged), the sink's
+// per-pair constants (1 / disc total, itwd, the two phase indices' origin
+// and cell density) are formed once per pair ahead of the barrier B0 and read
+// from LDS, not once per wave or per disc lane, and an item's ring comes from
+// a table (kRingOf), not from a square root or a division.
+#ifndef LFG_PAIR_SINK_MERGE
+#define LFG_PAIR_SINK_MERGE 1
+#endif
 
 // Diagnostic builds that read device counters back (lfg_debug_*,
 // lfg_diag_iters) keep every kernel in this translation unit (see
@@ -611,10 +623,14 @@ constexpr int U_MAIN = U_WD + U_DISC + U_DON;
 
 __device__ __forceinline__ int wd_ring_of(int u)  // ring of unique WD tile u (ring ir starts at 2 ir^2)
 {
+#if LFG_PAIR_SINK_MERGE
+    return kRingOf[u];
+#else
     int ir = int(sqrt(u * 0.5));
     if (2 * (ir + 1) * (ir + 1) <= u) ++ir;
     if (2 * ir * ir > u) --ir;
     return ir;
+#endif
 }
 
 // element weights (MODEL_SPEC 5.1-5.3): per WD ring, per disc ring, per spot element
@@ -698,7 +714,9 @@ struct ElemOut {
 // i, i = 0..NDISC_R, consecutive lanes of one wave: lane i holds the boundary
 // term P(r_i) and ring i's weight is the difference of neighbours (one pow
 // per lane of one wave, instead of two in a ring-start lane of every disc wave)
-template <typename GPtr>
+// (k_pair, LFG_PAIR_SINK_MERGE: the total's lane also writes its reciprocal,
+// which every disc lane of the sink formed for itself, to wtd[NDISC_R + 1])
+template <bool RCP = false, typename GPtr>
 __device__ __forceinline__ void ring_weight_lane(int rb, GPtr G, double* __restrict__ wtd)
 {
     const double P = disc_boundary(rb, G);
@@ -707,6 +725,7 @@ __device__ __forceinline__ void ring_weight_lane(int rb, GPtr G, double* __restr
     const double Pt = __shfl(P, l0 + NDISC_R, 64);
     if (rb < NDISC_R) wtd[rb] = (TWO_PI / NDISC_AZ) * (Pn - P);
     if (rb == 0) wtd[NDISC_R] = TWO_PI * (Pt - P);
+    if (RCP && rb == 0) wtd[NDISC_R + 1] = 1.0 / (TWO_PI * (Pt - P));
 }
 
 // results of an item go to a sink: wd_disc(u, a, b), spot(j, a, b, w),
@@ -830,7 +849,11 @@ __device__ __forceinline__ void element_item_to(int v, GPtr G, Sink& K)
         Pz = rw * (rc * sp * s + mu0 * c);
     } else if (u < U_WD + U_DISC) {  // disc (MODEL_SPEC 5.2), alpha in (0, pi)
         const int uu = u - U_WD;
+#if LFG_PAIR_SINK_MERGE
+        const int ir = kRingOf[u] - NWD_RINGS, j = uu - ir * (NDISC_AZ / 2);
+#else
         const int ir = uu / (NDISC_AZ / 2), j = uu - ir * (NDISC_AZ / 2);
+#endif
         const double rin = G[G_RWD];
         const double rc = rin + (ir + 0.5) * ((G[G_RDISC] - rin) / NDISC_R);
         Px = rc * kDiscCos[j];
@@ -1193,111 +1216,10 @@ __device__ inline void combine_after(const LikeArgs& L, int pair)
 // Whole-covered runs go into a difference array, partly covered points get
 // w |[a,b] n [lo,hi]| / (hi - lo) directly.  Sums are 2^-61 fixed point in
 // int64 so LDS atomics add them exactly, independent of order.
-constexpr int LIKE_THREADS = 512;
 constexpr int ACC_LDS = 24;  // proposal coordinates of the fused acceptance kept in LDS (the rest re-read)
 #ifndef LIKE_MINW
 #define LIKE_MINW 4  // minimum waves per SIMD: two 512-lane blocks per CU (<= 128 VGPRs; LDS < 80 KB)
 #endif
-constexpr int LIKE_TILE = LIKE_THREADS;  // one point per thread per tile
-constexpr int LIKE_NC = 2 * LIKE_TILE;   // cells of the phase index
-#ifndef LFG_WALK
-#define LFG_WALK 2  // unrolled forward steps of the cell walk before the loop
-#endif
-constexpr double FX_SCALE = 2305843009213693952.0;  // 2^61
-constexpr double FX_INV = 1.0 / FX_SCALE;
-
-struct PhaseIndex {  // sorted phases v[0..m) with a uniform-cell start table
-    const double* v;
-    const int* cell;
-    int m;
-    double t0, ginv;
-};
-
-__device__ __forceinline__ int cell_of(const PhaseIndex& X, double v)
-{
-    const double u = (v - X.t0) * X.ginv;
-    return u <= 0.0 ? 0 : (u >= double(LIKE_NC) ? LIKE_NC : int(u));
-}
-
-// #{v_p < x} (or #{v_p <= x} when LE).  cell[ci(x)] counts the points whose
-// cell index is below x's, all of which lie below x (ci is monotone), so the
-// walk only goes forward: usually zero or one point, two unrolled steps
-template <bool LE>
-__device__ __forceinline__ int count_below(const PhaseIndex& X, double x)
-{
-    int j = X.cell[cell_of(X, x)];
-    const int last = X.m - 1;
-    bool adv = false;
-#pragma unroll
-    for (int k = 0; k < LFG_WALK; ++k) {
-        const double vj = X.v[min(j, last)];
-        adv = (j <= last) & (LE ? (vj <= x) : (vj < x));
-        j += adv ? 1 : 0;
-    }
-    if (adv)  // clustered points: keep walking
-        while (j <= last && (LE ? (X.v[j] <= x) : (X.v[j] < x))) ++j;
-    return j;
-}
-
-// count_below<false> for Q queries in lockstep, so that their LDS chains overlap
-template <int Q>
-__device__ __forceinline__ void count_lt_multi(const PhaseIndex& X, const double (&x)[Q], int (&j)[Q])
-{
-    const int last = X.m - 1;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) j[q] = X.cell[cell_of(X, x[q])];
-    bool adv[Q];
-#pragma unroll
-    for (int k = 0; k < LFG_WALK; ++k) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const double vj = X.v[min(j[q], last)];
-            adv[q] = (j[q] <= last) & (vj < x[q]);
-            j[q] += adv[q] ? 1 : 0;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-        if (adv[q])
-            while (j[q] <= last && X.v[j[q]] < x[q]) ++j[q];
-}
-
-// count_le_back for Q queries in lockstep
-template <int Q>
-__device__ __forceinline__ void count_le_back_multi(const double* __restrict__ hi, const double (&x)[Q],
-                                                    const int (&J)[Q], int (&out)[Q])
-{
-    bool back[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        back[q] = (J[q] > 0) & (hi[max(J[q] - 1, 0)] > x[q]);
-        out[q] = J[q] - (back[q] ? 1 : 0);
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-        if (back[q])
-            while (out[q] > 0 && hi[out[q] - 1] > x[q]) --out[q];
-}
-
-// #{hi <= x} given J = #{lo < x}: hi > lo, so the answer is <= J; the points
-// straddling x (usually one) are stepped over backwards
-__device__ __forceinline__ int count_le_back(const double* __restrict__ hi, int J, double x)
-{
-    const bool back = (J > 0) & (hi[max(J - 1, 0)] > x);
-    J -= back ? 1 : 0;
-    if (back)
-        while (J > 0 && hi[J - 1] > x) --J;
-    return J;
-}
-
-// cell[g] = #{p : ci(v_p) < g} with ci(v) = floor((v - t0) ginv) clamped to
-// [-1, NC] exactly as cell_of computes it: point p fills the cells
-// (ci(v_{p-1}), ci(v_p)], the last point also the cells above its own
-__device__ __forceinline__ PhaseIndex phase_index(const double* v, const int* cell, int m)
-{
-    const double span = v[m - 1] - v[0];
-    return PhaseIndex{v, cell, m, v[0], span > 0.0 ? LIKE_NC / span : 0.0};
-}
 
 __device__ __forceinline__ void build_cells(const double* __restrict__ v, int m, int* __restrict__ cell, int tid)
 {
@@ -1315,121 +1237,44 @@ __device__ __forceinline__ void build_cells(const double* __restrict__ v, int m,
     }
 }
 
-__device__ __forceinline__ long long to_fx(double x) { return static_cast<long long>(rint(x * FX_SCALE)); }
-
 __device__ __forceinline__ void fx_add(unsigned long long* acc, int p, long long q)
 {
     atomicAdd(acc + p, static_cast<unsigned long long>(q));
 }
 
-// the runs of element [a, b] over the tile's windows [lo_p, hi_p] (lo, hi
-// sorted, hi >= lo): it overlaps [P1, P4) and covers [P2, P3) whole.  A
-// zero-width window is a point: covered when a <= ph <= b, never partial.
-struct Runs {
-    int P1, P2, P3, P4;
+// the sweep's entries (lfg_sweep.hpp) into an LDS difference array
+struct FxAdd {
+    unsigned long long* acc;
+    __device__ __forceinline__ void operator()(int p, long long q) const { fx_add(acc, p, q); }
 };
 
-__device__ __forceinline__ Runs element_runs(double a, double b, const PhaseIndex& X, const double* __restrict__ hi)
-{
-    Runs R;
-    R.P2 = count_below<false>(X, a);
-    R.P4 = count_below<false>(X, b);
-    R.P1 = count_le_back(hi, R.P2, a);
-    R.P3 = count_le_back(hi, R.P4, b);
-    return R;
-}
-
-// adds wn * (covered fraction) of element [a, b] given its runs
 __device__ __forceinline__ void apply_runs(const Runs& R, double a, double b, double wn, const PhaseIndex& X,
                                            const double* __restrict__ hi, const double* __restrict__ iw,
                                            unsigned long long* acc)
 {
-    const int P1 = R.P1, P2 = R.P2, P3 = R.P3, P4 = R.P4;
-    int e0 = P4, s1 = P4;  // partial runs [P1, e0) and [s1, P4)
-    if (P2 < P3) {         // whole-covered run (slot m is never read)
-        const long long q = to_fx(wn);
-        fx_add(acc, P2, q);
-        if (P3 < X.m) fx_add(acc, P3, -q);
-        e0 = P2;
-        s1 = P3;
-    }
-    for (int r = 0; r < 2; ++r) {
-        const int pe = r ? P4 : e0;
-        for (int p = r ? s1 : P1; p < pe; ++p) {
-            const double ov = fmin(b, hi[p]) - fmax(a, X.v[p]);
-            if (ov > 0.0) {
-                const long long q = to_fx(wn * ov * iw[p]);
-                fx_add(acc, p, q);
-                if (p + 1 < X.m) fx_add(acc, p + 1, -q);
-            }
-        }
-    }
+    lfg::apply_runs(R, a, b, wn, X, hi, iw, FxAdd{acc});
 }
 
-// apply_runs for NI intervals of one lane with every LDS read issued before
-// the first atomic: a read waits for all the lane's earlier LDS operations
-// (one in-order counter), so reads between atomics waited for each atomic's
-// round trip.  The first K windows of each partial run are read up front
-// (windows that tile the phase axis give one at each end); longer partial
-// runs finish one window at a time after the atomics.  The same entries as
-// apply_runs: identical integer sums.
 template <int NI>
 __device__ __forceinline__ void apply_runs_batched(const Runs (&R)[NI], const double (&a)[NI], const double (&b)[NI],
                                                    double wn, const PhaseIndex& X, const double* __restrict__ hi,
                                                    const double* __restrict__ iw, unsigned long long* acc)
 {
-    constexpr int K = 2;
-    const int last = X.m - 1;
-    int ps[NI][2], pn[NI][2];
-    long long q[NI][2][K];
-#pragma unroll
-    for (int k = 0; k < NI; ++k) {
-        const bool whole = R[k].P2 < R[k].P3;
-        const int e0 = whole ? R[k].P2 : R[k].P4, s1 = whole ? R[k].P3 : R[k].P4;
-        ps[k][0] = R[k].P1;
-        pn[k][0] = e0 - R[k].P1;
-        ps[k][1] = s1;
-        pn[k][1] = R[k].P4 - s1;
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                const int p = min(ps[k][e] + i, last);
-                const double ov = fmin(b[k], hi[p]) - fmax(a[k], X.v[p]);
-                q[k][e][i] = (i < pn[k][e] && ov > 0.0) ? to_fx(wn * ov * iw[p]) : 0;
-            }
-    }
-    const long long qw = to_fx(wn);
-#pragma unroll
-    for (int k = 0; k < NI; ++k) {
-        if (R[k].P2 < R[k].P3) {
-            fx_add(acc, R[k].P2, qw);
-            if (R[k].P3 < X.m) fx_add(acc, R[k].P3, -qw);
-        }
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                const int p = ps[k][e] + i;
-                if (q[k][e][i] != 0) {
-                    fx_add(acc, p, q[k][e][i]);
-                    if (p + 1 < X.m) fx_add(acc, p + 1, -q[k][e][i]);
-                }
-            }
-    }
-#pragma unroll
-    for (int k = 0; k < NI; ++k)
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-            for (int p = ps[k][e] + K; p < ps[k][e] + pn[k][e]; ++p) {
-                const double ov = fmin(b[k], hi[p]) - fmax(a[k], X.v[p]);
-                if (ov > 0.0) {
-                    const long long qq = to_fx(wn * ov * iw[p]);
-                    fx_add(acc, p, qq);
-                    if (p + 1 < X.m) fx_add(acc, p + 1, -qq);
-                }
-            }
+    lfg::apply_runs_batched<NI>(R, a, b, wn, X, hi, iw, FxAdd{acc});
 }
+
+#if LFG_PAIR_SINK_MERGE
+// k_pair's sinks: the run ends' adjacent entries summed before they are
+// added, where no lane of the wave has a run end of two windows or more (one
+// vote of the lanes that hold an eclipsed item; a lane without one is not there)
+template <int NI>
+__device__ __forceinline__ void apply_runs_merged(const Runs (&R)[NI], const double (&a)[NI], const double (&b)[NI],
+                                                  double wn, const PhaseIndex& X, const double* __restrict__ hi,
+                                                  const double* __restrict__ iw, unsigned long long* acc)
+{
+    lfg::apply_runs_merged<NI>(R, a, b, wn, X, hi, iw, FxAdd{acc}, [](bool slow) { return __any(slow) != 0; });
+}
+#endif
 
 // ring of unique WD/disc item u: WD ring r holds 2 r^2 <= u < 2 (r + 1)^2,
 // disc rings follow (NDISC_AZ / 2 items each)
@@ -1440,6 +1285,18 @@ __device__ __forceinline__ int uring(int u)
     r += (2 * (r + 1) * (r + 1) <= u) ? 1 : 0;
     r -= (2 * r * r > u) ? 1 : 0;
     return r;
+}
+
+// the same from the table (k_pair, LFG_PAIR_SINK_MERGE).  k_lnlike keeps
+// uring: with the table's load in its sweep the TAB instantiations went from
+// 0 / 16 to 16 / 32 B of scratch per lane
+__device__ __forceinline__ int pair_ring(int u)
+{
+#if LFG_PAIR_SINK_MERGE
+    return kRingOf[u];
+#else
+    return uring(u);
+#endif
 }
 
 // inclusive wave prefix sum: Hillis-Steele within each row of 16 lanes
@@ -2891,8 +2748,12 @@ struct PairSink {
             return;
         }
         if (!(a < b)) return;
-        const int ir = uring(u);
+        const int ir = pair_ring(u);
+#if LFG_PAIR_SINK_MERGE
+        const double wn = (u < U_WD) ? wd_ring_weight(ir, ul) * itwd : swt[ir - NWD_RINGS] * swt[NDISC_R + 1];
+#else
         const double wn = (u < U_WD) ? wd_ring_weight(ir, ul) * itwd : swt[ir - NWD_RINGS] * (1.0 / swt[NDISC_R]);
+#endif
         double q[4] = {a, b, -b, -a};  // the element and its mirror [-b, -a]
         int J[4], Jb[4];
         count_lt_multi<4>(XW, q, J);
@@ -2900,7 +2761,11 @@ struct PairSink {
         unsigned long long* A = ((lane & 1) ? acc2 : acc)[(u < U_WD) ? 0 : 1];
         const Runs RR[2] = {Runs{Jb[0], J[0], Jb[1], J[1]}, Runs{Jb[2], J[2], Jb[3], J[3]}};
         const double aa[2] = {a, -b}, bb[2] = {b, -a};
+#if LFG_PAIR_SINK_MERGE
+        apply_runs_merged<2>(RR, aa, bb, wn, XW, hi, iw, A);
+#else
         apply_runs_batched<2>(RR, aa, bb, wn, XW, hi, iw, A);
+#endif
     }
     __device__ __forceinline__ void spot(int j, double a, double b, double w)
     {
@@ -2914,7 +2779,11 @@ struct PairSink {
 #endif
             const Runs RR[1] = {element_runs(a, b, XW, hi)};
             const double aa[1] = {a}, bb[1] = {b};
+#if LFG_PAIR_SINK_MERGE
+            apply_runs_merged<1>(RR, aa, bb, w * PAIR_SPOT_S, XW, hi, iw, acc[2]);
+#else
             apply_runs_batched<1>(RR, aa, bb, w * PAIR_SPOT_S, XW, hi, iw, acc[2]);
+#endif
         }
     }
     __device__ __forceinline__ void donor(int uu, double vx0, double vy0, double vz0, double cen0, double hw0)
@@ -3581,7 +3450,7 @@ __device__ __forceinline__ void long_tables(LongTabs& W, SubTables& T, SubEntrie
     auto wd_entry = [&](int g, double2& ab, int& t, long long& q) {
         ab = abw[g];
         if (!(ab.x < ab.y)) return false;
-        const int u = uitem(g), ir = uring(u);
+        const int u = uitem(g), ir = pair_ring(u);
         t = u < U_WD ? 0 : 1;
         q = to_fx(u < U_WD ? wd_ring_weight(ir, ul) * itwd : swt[ir - NWD_RINGS] * (1.0 / swt[NDISC_R]));
         return true;
@@ -3870,7 +3739,15 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
     static_assert(!(GP && LONG), "GP trees keep the one-tile layout or the two kernels");
     const LikeArgs& L = A.L;
     const ElemSpec& X = A.X;
+#if LFG_PAIR_SINK_MERGE
+    // disc ring weights, the disc total and (one-tile sinks) its reciprocal (prologue)
+    __shared__ double swt[NDISC_R + (LONG ? 1 : 2)];
+    // the sinks' per-pair constants (wave 6, ahead of B0): itwd, then t0 and
+    // ginv of the windows' and of the point phases' index (phase_index)
+    __shared__ double skc[5];
+#else
     __shared__ double swt[NDISC_R + 1];           // disc ring weights and the disc total (prologue)
+#endif
     __shared__ double sbw[NBS];
     __shared__ double2 sab[NBS];
     __shared__ double sdq[U_DON * DON_STRIDE];
@@ -4036,7 +3913,8 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
         }
     } else {
 #if LFG_PAIR_RUNSCAN
-        // the sinks add at indices < m only (apply_runs_batched, donor, flush)
+        // the sinks add at indices < m only (apply_runs_batched and
+        // apply_runs_merged, donor, flush)
         // and run_scan reads [0, m): the slots above m stay as they are, and
         // a wave wholly above m stores nothing
         if (tid <= m) {
@@ -4063,7 +3941,31 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
     }
     PAIR_STAMP(19, tid == 0);
     // the disc ring weights (MODEL_SPEC 5.2): wave 7's lanes 0..NDISC_R
+#if LFG_PAIR_SINK_MERGE
+    if (st == ST_OK && wv == 7 && lane <= NDISC_R) ring_weight_lane<!LONG>(lane, Gc, swt);
+    // the sinks' constants, once per pair and not once per wave: phase_index's
+    // and itwd's expressions on the first and last windows, which every
+    // thread holds (lane 0: itwd; 1: the windows' lo; 2: the point phases;
+    // one IEEE quotient for the three).  Wave 6: wave 7's prologue is the
+    // longest (the ring weights' pow), and B0 waits for it
+    if (!LONG && st == ST_OK && m > 0 && wv == 6 && lane < 3) {
+        double ph0, lo0, hi0, hw0, ph1, lo1, hi1, hw1;
+        pair_window(xw_0, ww_0, phi0, ph0, lo0, hi0, hw0);
+        pair_window(xw_1, ww_1, phi0, ph1, lo1, hi1, hw1);
+        const double ulk = Gc[G_ULIMB];
+        const double v0 = lane == 1 ? lo0 : ph0, span = (lane == 1 ? lo1 : ph1) - v0;
+        const double num = lane ? double(LIKE_NC) : 1.0;
+        const double den = lane ? span : TWO_PI * ((1.0 - ulk) * 0.5 + ulk / 3.0);
+        const double quo = num / den;
+        if (lane == 0) skc[0] = quo;
+        else {
+            skc[2 * lane - 1] = v0;
+            skc[2 * lane] = span > 0.0 ? quo : 0.0;
+        }
+    }
+#else
     if (st == ST_OK && wv == 7 && lane <= NDISC_R) ring_weight_lane(lane, Gc, swt);
+#endif
     __syncthreads();  // B0: windows, cells, flags, zeroed sums, ring weights, sjob
     PAIR_STAMP(16, tid == 0);
 
@@ -4223,14 +4125,25 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_pair(PairArgs A)
     }
     if (st == ST_OK && m > 0) {
         const double ul = Gc[G_ULIMB];
+#if LFG_PAIR_SINK_MERGE
+        const double itwd = LONG ? 1.0 / (TWO_PI * ((1.0 - ul) * 0.5 + ul / 3.0)) : skc[0];
+#else
         const double itwd = 1.0 / (TWO_PI * ((1.0 - ul) * 0.5 + ul / 3.0));
+#endif
         auto make_sink = [&]() {
             if constexpr (LONG)  // the point-major sinks only (no tile arrays in this instantiation)
                 return PairSink{true, lane, PhaseIndex{}, PhaseIndex{}, nullptr, nullptr, nullptr, nullptr, stot, swt,
                                 ul, itwd, Gc[G_S], Gc[G_C], Lab, sab, sbw, sdq};
+#if LFG_PAIR_SINK_MERGE
+            else
+                return PairSink{dir, lane, PhaseIndex{TA.lo, TA.cell, m, skc[1], skc[2]},
+                                PhaseIndex{sph, SU.s.scp, m, skc[3], skc[4]}, TA.hi,
+                                TA.iw, sacc, SU.s.X, stot, swt, ul, itwd, Gc[G_S], Gc[G_C], SU.ab, sab, sbw, sdq};
+#else
             else
                 return PairSink{dir, lane, phase_index(TA.lo, TA.cell, m), phase_index(sph, SU.s.scp, m), TA.hi,
                                 TA.iw, sacc, SU.s.X, stot, swt, ul, itwd, Gc[G_S], Gc[G_C], SU.ab, sab, sbw, sdq};
+#endif
         };
         PairSink K = make_sink();
         // chunk c: items v = 64 c + lane of one region each (c < 11: WD and
