@@ -104,7 +104,9 @@ struct lfg_tree {
      *   uniform           c0 = ln(1 / |p1 - p2|)
      *   log_uniform, mod_jeff  c0 = -ln(normalise)
      * (lfit_python_amd.batch.prior_consts).  NULL: each term from
-     * prior_p1/p2/norm directly. */
+     * prior_p1/p2/norm directly.  Both give -inf for a Gaussian term once
+     * the reference's pdf underflows (MODEL_SPEC 8); where that pdf is a
+     * denormal the NULL path's log(pdf) is coarse, as the reference's is. */
     const double* prior_c;
 };
 

@@ -453,8 +453,11 @@ __device__ inline void prior_lane(const SetupArgs& A, int w)
                     const double fm = frexp((ty == 3) ? v[k] : (ty == 4 ? v[k] + p1 : 1.0), &fe);
                     prod *= fm;
                     pex += fe;
-                    // scipy's pdf underflows to 0 (log -> -inf) below e^-745.13
-                    ok = ok && ((ty <= 1) ? (term > PDF_LN_MIN && (ty == 0 || v[k] > 0.0))
+                    // scipy's pdf underflows to 0 (log -> -inf) once the unit
+                    // normal's density e = term + ln p2 or its quotient by p2 (term) is
+                    // below e^-745.13: e decides for p2 < 1 (c1 > 1), -ln p2 = c0 + ln sqrt(2 pi)
+                    const double thr = (A.prior_c[2 * d + 1] > 1.0) ? PDF_LN_MIN + (c0 + LN_SQRT_2PI) : PDF_LN_MIN;
+                    ok = ok && ((ty <= 1) ? (term > thr && (ty == 0 || v[k] > 0.0))
                                           : (ty == 4 ? (v[k] > 0.0 && v[k] < p2)
                                                      : (ty <= 3 && v[k] > p1 && v[k] < p2)));
                 }

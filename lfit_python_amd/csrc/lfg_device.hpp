@@ -1608,8 +1608,11 @@ __device__ inline double prior_lnprob(int type, double p1, double p2, double nor
     return -INFINITY;
 }
 
-// ln of the smallest positive double (a denormal): below it scipy's pdf is
-// 0 and log(pdf) -inf (model.py:85-89)
+// ln of half the smallest positive double (a denormal): what lies below it
+// rounds to 0.  scipy's pdf is (exp(-z^2/2) / sqrt(2 pi)) / p2 (model.py:85-89),
+// so log(pdf) is -inf once e = -z^2/2 - ln sqrt(2 pi) or e - ln p2 falls below
+// it (MODEL_SPEC 8): the first decides for p2 < 1, the second for p2 > 1
 constexpr double PDF_LN_MIN = -745.1332191019412;
+constexpr double LN_SQRT_2PI = 0.91893853320467274178;
 
 }  // namespace lfg
