@@ -51,7 +51,8 @@ double disc_boundary(int i, const Pair& G)
 {
     const double r = G.rwd_a + i * ((G.rdisc_a - G.rwd_a) / NDISC_R);
     const double ex = 2.0 - G.dexp;
-    return (std::fabs(ex) < 1e-10) ? std::log(r) : std::pow(r, ex) / ex;
+    const double lr = std::log(r / G.rwd_a);  // lfg.hip disc_boundary: the integral from the inner edge
+    return (std::fabs(ex) < 1e-10) ? lr : std::pow(G.rwd_a, ex) * std::expm1(ex * lr) / ex;
 }
 
 // k_setup's setup lane and stream lane for one (walker, eclipse): status and
@@ -119,6 +120,7 @@ int setup_pair(const double* pin, int np, Pair& G, double& rprior)
     G.reff = eggleton(R.q);
     const double sce = G.s * std::cos(PI * p[5]);
     G.rcal = std::sqrt(1.0 - sce * sce);
+    if (l1_out_of_reach(R, G.s, G.c, G.rwd_a, G.rdisc_a)) G.rcal = -G.rcal;  // as k_setup's G_RCAL
     G.wdf = p[0]; G.df = p[1]; G.sf = p[2]; G.rsf = p[3];
     G.inc = inc;
     return ST_OK;
@@ -255,7 +257,7 @@ void elements(const Pair& G, Tables& T)
         tot += T.sw[j];
         const double off = G.L * (uk - G.upk);
         LFC_NIT
-        element_interval_fast(R, std::fma(off, G.caz, G.bsx), std::fma(off, G.saz, G.bsy), 0.0, s, c, G.rcal, G.reff,
+        element_interval_fast(R, std::fma(off, G.caz, G.bsx), std::fma(off, G.saz, G.bsy), 0.0, s, c, std::fabs(G.rcal), G.reff,
                               T.sa[j], T.sb[j] LFC_NITARGS);
         LFC_COST(U_WD + U_DISC + j);
         LFC_AB(T.sa[j], T.sb[j]);

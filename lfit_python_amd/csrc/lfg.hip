@@ -572,7 +572,9 @@ __device__ __forceinline__ void setup_any(const SetupArgs& A, int t)
     G[G_S] = s; G[G_C] = c; G[G_INC] = inc;
     G[G_BDEN] = fis + (1.0 - fis) * fmax(nmax, 0.0);
     const double sce = s * cos(PI * dphi);
-    G[G_RCAL] = sqrt(1.0 - sce * sce);
+    // (negative: no WD or disc element's line of sight comes near L1, element_interval_fast)
+    const double rcal = sqrt(1.0 - sce * sce);
+    G[G_RCAL] = l1_out_of_reach(R, s, c, G[G_RWD], G[G_RDISC]) ? -rcal : rcal;
     if (A.gp) {
         // SimpleGPEclipse.create_GP / calcChangepoints (CVModel.py:529-648):
         // amplitudes exp(ln_amp), metric exp(ln_tau); the changepoint
@@ -647,7 +649,10 @@ __device__ inline double disc_boundary(int i, GPtr G)
     const double rin = G[G_RWD];
     const double r = rin + i * ((G[G_RDISC] - rin) / NDISC_R);
     const double ex = 2.0 - G[G_DEXP];
-    return (fabs(ex) < 1e-10) ? log(r) : pow(r, ex) / ex;
+    // the integral of r^(1 - dexp) from the inner edge, as rin^ex expm1(ex ln(r / rin)) / ex: the difference of
+    // two powers, r^ex / ex - rin^ex / ex, loses 1 / (ex ln(r1 / r0)) of its digits as dexp -> 2
+    const double lr = log(r / rin);
+    return (fabs(ex) < 1e-10) ? lr : pow(rin, ex) * expm1(ex * lr) / ex;
 }
 
 template <typename GPtr>
@@ -841,7 +846,7 @@ __device__ __forceinline__ void element_item_to(int v, GPtr G, Sink& K)
     }
 
     // the element of unique item u (its mirror's interval is implied)
-    double Px, Py, Pz;
+    double Px, Py, Pz, rcal = G[G_RCAL];
     if (u < U_WD) {  // white dwarf tile (MODEL_SPEC 5.1), cos(psi) > 0 half
         const int ir = wd_ring_of(u);
         const double rc = kWdRc[ir], mu0 = kWdMu0[ir];
@@ -869,6 +874,7 @@ __device__ __forceinline__ void element_item_to(int v, GPtr G, Sink& K)
         Px = fma(off, G[G_CAZ], G[G_BSX]);
         Py = fma(off, G[G_SAZ], G[G_BSY]);
         Pz = 0.0;
+        rcal = fabs(rcal);  // the strip is not bound by the disc's radius: test each element for L1
     }
     double a, b;
 #ifdef LFG_COUNT_ITERS
@@ -877,7 +883,7 @@ __device__ __forceinline__ void element_item_to(int v, GPtr G, Sink& K)
     bool fb = false;
     int nit[3] = {0, 0, 0};
     double gs[2] = {0.0, 0.0};
-    element_interval_fast(R, Px, Py, Pz, s, c, G[G_RCAL], G[G_REFF], a, b, &fb, nit, gs);
+    element_interval_fast(R, Px, Py, Pz, s, c, rcal, G[G_REFF], a, b, &fb, nit, gs);
     {
         const int reg = (u < U_WD) ? 0 : (u < U_WD + U_DISC ? 1 : 2);
         unsigned long long* C = g_iter_dbg + reg * 16;
@@ -903,7 +909,7 @@ __device__ __forceinline__ void element_item_to(int v, GPtr G, Sink& K)
         }
     }
 #else
-    element_interval_fast(R, Px, Py, Pz, s, c, G[G_RCAL], G[G_REFF], a, b);
+    element_interval_fast(R, Px, Py, Pz, s, c, rcal, G[G_REFF], a, b);
 #endif
     K.mark();
     if (u >= U_MAIN) K.spot(u - U_MAIN, a, b, bs_weight(u - U_MAIN, G));

@@ -22,6 +22,7 @@ constexpr double LN2 = 0.69314718055994530942;
 // MODEL_SPEC.md section 7
 constexpr double RAY_TOL = 1e-13;
 constexpr int RAY_MAXIT = 100;
+constexpr double RAY_NEAR_L1 = 0.05;  // lines of sight this close to L1 (units of Rs): 5 x the 0.0093 of MODEL_SPEC 4.2
 constexpr double TH_TOL = 1e-13;
 constexpr int ROOT_MAXIT = 100;
 // 1-D safeguarded Newton (L1, donor radius, stream crossing) stops after a
@@ -230,6 +231,14 @@ __device__ inline double eggleton(double q)
 // MODEL_SPEC 4.2: minimum of Phi along P + t e over the chord of the sphere
 // |X - D| <= Rs.  Uses X.e = P.e + t (|e| = 1) so each Newton iteration
 // needs two rsqrt and one division.
+// STARTS = 1: safeguarded Newton from the warm start, the bracket kept by the
+// sign of dPhi/dt.  That finds the minimum where Phi has one well on the
+// chord.  Next to L1 it can have two, a dip beside the saddle and the donor's
+// well, or rise from the chord's start to a maximum before the well (MODEL_SPEC
+// 4.2), and the warm start keeps whichever it was given.  STARTS = 3 (the
+// nested solver behind element_interval_fast) also starts at the chord's
+// start and at the closest approach to D, and takes the lowest of the three.
+template <int STARTS = 1>
 __device__ inline bool ray_min(const Roche& R, double Px, double Py, double Pz,
                                double ex, double ey, double ez, double& tw, double& fmin)
 {
@@ -238,41 +247,46 @@ __device__ inline bool ray_min(const Roche& R, double Px, double Py, double Pz,
     const double b2 = ux * ux + uy * uy + uz * uz - tc * tc;
     if (b2 >= R.Rs2) return false;
     const double h = sqrt(R.Rs2 - b2);
-    double lo = tc - h, hi = tc + h;
-    if (hi <= 0.0) return false;
-    lo = fmax(lo, 0.0);
-    double t = tw;
-    if (!(t > lo && t < hi)) t = (tc > lo && tc < hi) ? tc : 0.5 * (lo + hi);
+    if (tc + h <= 0.0) return false;
     const double Pe = Px * ex + Py * ey + Pz * ez;
     const double exy2 = 2.0 * (ex * ex + ey * ey);
-    for (int it = 0; it < RAY_MAXIT; ++it) {
-        const double x = fma(t, ex, Px), y = fma(t, ey, Py), z = fma(t, ez, Pz);
-        const double r1s = x * x + y * y + z * z;
-        const double ir1 = rsqrt(r1s);
-        const double ir1s = ir1 * ir1;
-        const double i1 = R.cA * ir1s * ir1;
-        const double dx = x - 1.0;
-        const double ir2 = rsqrt(dx * dx + y * y + z * z);
-        const double ir2s = ir2 * ir2;
-        const double i2 = R.cB * ir2s * ir2;
-        const double p1 = Pe + t;
-        const double p2 = p1 - ex;
-        const double f1 = i1 * p1 + i2 * p2 - 2.0 * ((x - R.mu) * ex + y * ey);
-        const double f2 = i1 * (1.0 - 3.0 * p1 * p1 * ir1s) + i2 * (1.0 - 3.0 * p2 * p2 * ir2s) - exy2;
-        if (f1 > 0.0) hi = t; else lo = t;
-        double tn = (f2 > 0.0) ? t - f1 / f2 : 0.5 * (lo + hi);
-        if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
-        const double d = tn - t;
-        t = tn;
-        if (fabs(d) <= RAY_TOL) break;
+    double tbest = 0.0, fbest = 0.0;
+    for (int k = 0; k < STARTS; ++k) {
+        double lo = fmax(tc - h, 0.0), hi = tc + h;
+        double t = (k == 0) ? tw : (k == 1 ? fma(1e-6, hi - lo, lo) : tc);
+        if (!(t > lo && t < hi)) t = (tc > lo && tc < hi) ? tc : 0.5 * (lo + hi);
+        for (int it = 0; it < RAY_MAXIT; ++it) {
+            const double x = fma(t, ex, Px), y = fma(t, ey, Py), z = fma(t, ez, Pz);
+            const double r1s = x * x + y * y + z * z;
+            const double ir1 = rsqrt(r1s);
+            const double ir1s = ir1 * ir1;
+            const double i1 = R.cA * ir1s * ir1;
+            const double dx = x - 1.0;
+            const double ir2 = rsqrt(dx * dx + y * y + z * z);
+            const double ir2s = ir2 * ir2;
+            const double i2 = R.cB * ir2s * ir2;
+            const double p1 = Pe + t;
+            const double p2 = p1 - ex;
+            const double f1 = i1 * p1 + i2 * p2 - 2.0 * ((x - R.mu) * ex + y * ey);
+            const double f2 = i1 * (1.0 - 3.0 * p1 * p1 * ir1s) + i2 * (1.0 - 3.0 * p2 * p2 * ir2s) - exy2;
+            if (f1 > 0.0) hi = t; else lo = t;
+            double tn = (f2 > 0.0) ? t - f1 / f2 : 0.5 * (lo + hi);
+            if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
+            const double d = tn - t;
+            t = tn;
+            if (fabs(d) <= RAY_TOL) break;
+        }
+        const double f = rpot(R, fma(t, ex, Px), fma(t, ey, Py), fma(t, ez, Pz));
+        if (k == 0 || f < fbest) { fbest = f; tbest = t; }
     }
-    tw = t;
-    fmin = rpot(R, fma(t, ex, Px), fma(t, ey, Py), fma(t, ez, Pz));
+    tw = tbest;
+    fmin = fbest;
     return true;
 }
 
 // g(theta) = min Phi - Phi_L1 along the line of sight at orbital angle theta
 // (MODEL_SPEC 4.3); dg by the envelope theorem.  Miss: g = +1, dg = 0.
+template <int STARTS = 1>
 __device__ inline bool g_eval(const Roche& R, double Px, double Py, double Pz,
                               double s, double c, double th, double& tw,
                               double& g, double& dg)
@@ -281,7 +295,7 @@ __device__ inline bool g_eval(const Roche& R, double Px, double Py, double Pz,
     sincos(th, &sn, &cs);
     const double ex = s * cs, ey = -s * sn;
     double fm;
-    if (!ray_min(R, Px, Py, Pz, ex, ey, c, tw, fm)) {
+    if (!ray_min<STARTS>(R, Px, Py, Pz, ex, ey, c, tw, fm)) {
         g = 1.0;
         dg = 0.0;
         return false;
@@ -293,6 +307,7 @@ __device__ inline bool g_eval(const Roche& R, double Px, double Py, double Pz,
     return true;
 }
 
+template <int STARTS = 1>
 __device__ inline double theta_root(const Roche& R, double Px, double Py, double Pz,
                                     double s, double c, double lo, double hi, bool pos_lo,
                                     double th, double& tw)
@@ -300,7 +315,7 @@ __device__ inline double theta_root(const Roche& R, double Px, double Py, double
     if (!(th > lo && th < hi)) th = 0.5 * (lo + hi);
     for (int it = 0; it < ROOT_MAXIT; ++it) {
         double g, dg;
-        g_eval(R, Px, Py, Pz, s, c, th, tw, g, dg);
+        g_eval<STARTS>(R, Px, Py, Pz, s, c, th, tw, g, dg);
         if ((g > 0.0) == pos_lo) lo = th; else hi = th;
         double tn = (dg != 0.0) ? th - g / dg : 0.5 * (lo + hi);
         if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
@@ -313,6 +328,7 @@ __device__ inline double theta_root(const Roche& R, double Px, double Py, double
 
 // MODEL_SPEC 4.3: eclipse interval [a, b] (phase units) of the point P.
 // Returns false (a = 1, b = -1) when P is never eclipsed.
+template <int STARTS = 1>
 __device__ inline bool element_interval(const Roche& R, double Px, double Py, double Pz,
                                         double s, double c, double Reff, double& a, double& b)
 {
@@ -329,7 +345,7 @@ __device__ inline bool element_interval(const Roche& R, double Px, double Py, do
     const double lo = thc - Dm, hi = thc + Dm;
 
     double tw = -1.0, g, dg;
-    bool chord = g_eval(R, Px, Py, Pz, s, c, thc, tw, g, dg);
+    bool chord = g_eval<STARTS>(R, Px, Py, Pz, s, c, thc, tw, g, dg);
     if (!chord) return false;
     double thi = thc;
     if (!(g < 0.0)) {
@@ -348,7 +364,7 @@ __device__ inline bool element_interval(const Roche& R, double Px, double Py, do
             if (fabs(tn - th) <= TH_TOL) break;
             if (chord) { pth = th; pdg = dg; have = true; }
             th = tn;
-            chord = g_eval(R, Px, Py, Pz, s, c, th, tw, g, dg);
+            chord = g_eval<STARTS>(R, Px, Py, Pz, s, c, th, tw, g, dg);
         }
         if (!found) return false;
     }
@@ -356,8 +372,8 @@ __device__ inline bool element_interval(const Roche& R, double Px, double Py, do
     const double ce = (sqrt(fmax(uu - Reff * Reff, 0.0)) - c * uz) / (s * uxy);
     de = (ce > -1.0 && ce < 1.0) ? acos(ce) : 0.5 * Dm;
     double twi = tw, two = tw;
-    const double thin = theta_root(R, Px, Py, Pz, s, c, lo, thi, true, thc - de, twi);
-    const double thout = theta_root(R, Px, Py, Pz, s, c, thi, hi, false, thc + de, two);
+    const double thin = theta_root<STARTS>(R, Px, Py, Pz, s, c, lo, thi, true, thc - de, twi);
+    const double thout = theta_root<STARTS>(R, Px, Py, Pz, s, c, thi, hi, false, thc + de, two);
     a = thin * (1.0 / TWO_PI);
     b = thout * (1.0 / TWO_PI);
     return true;
@@ -552,6 +568,38 @@ __device__ inline void tangency_pair(const Roche& R, double Px, double Py, doubl
         if (B.st == 0) B = B2;
         if (A.st != 0 && B.st != 0) break;
     }
+}
+
+// squared distance of L1 from the line P + t e, t kept inside [lo, hi]
+__device__ __forceinline__ double ray_l1_dist2(const Roche& R, double Px, double Py, double Pz, double ex, double ey,
+                                               double ez, double lo, double hi)
+{
+    const double wx = R.xl1 - Px;
+    const double tl = fmin(fmax(wx * ex - Py * ey - Pz * ez, lo), hi);
+    const double lx = fma(tl, ex, -wx), ly = fma(tl, ey, Py), lz = fma(tl, ez, Pz);
+    return lx * lx + ly * ly + lz * lz;
+}
+
+// Can a line of sight from P pass L1 within RAY_NEAR_L1 Rs at all?  The
+// closest one points at L1 in the plane and misses it by |c |w_xy| - s w_z|,
+// w = L1 - P = u - (Rs, 0, 0), u = D - P.  Few elements can (none of a disc
+// inside 0.6 x_L1 at i < 87), and only their contacts are tested.
+__device__ __forceinline__ bool tangency_may_pass_l1(const Roche& R, double ux, double uz, double uxy2, double s,
+                                                     double c)
+{
+    const double wxy2 = fma(R.Rs, R.Rs - 2.0 * ux, uxy2), near = fma(s, fabs(uz), RAY_NEAR_L1 * R.Rs);
+    return c * c * wxy2 < near * near;
+}
+
+// A tangency is the contact only if no other stretch of its line of sight is
+// inside the lobe.  Next to L1 Phi can have two wells on one chord (ray_min),
+// and the tangency of the one says nothing about the other: a contact whose
+// line of sight passes L1 within RAY_NEAR_L1 Rs goes to the nested solver,
+// whose ray minimum starts from both wells there (ray_min<3>).
+__device__ __forceinline__ bool tangency_near_l1(const Roche& R, double Px, double Py, double Pz, double s, double c,
+                                                 const Tan& T)
+{
+    return ray_l1_dist2(R, Px, Py, Pz, s * T.cs, -s * T.sn, c, 0.0, 1e300) < RAY_NEAR_L1 * RAY_NEAR_L1 * R.Rs2;
 }
 
 // t at the ray's minimum of Phi, one Newton step from the closest approach
@@ -774,6 +822,17 @@ __device__ __forceinline__ double root_open32(const Roche& R, double dx, double 
 }
 #endif  // LFG_F32_OPEN
 
+// Whether no WD or disc element of a pair has a line of sight that passes L1
+// within RAY_NEAR_L1 Rs.  Such an element lies within rdisc_a of the WD and
+// within rwd_a of the plane, so w = L1 - P has |w_xy| >= xl1 - rdisc_a and
+// |w_z| <= rwd_a, and its closest line of sight misses L1 by
+// |c |w_xy| - s w_z| >= c (xl1 - rdisc_a) - s rwd_a.  (Bright-spot elements
+// reach further out: they are tested one by one.)
+__device__ __forceinline__ bool l1_out_of_reach(const Roche& R, double s, double c, double rwd_a, double rdisc_a)
+{
+    return c * (R.xl1 - rdisc_a) >= fma(s, rwd_a, RAY_NEAR_L1 * R.Rs);
+}
+
 // 0: not eclipsed, 1: eclipsed, -1: undecided (use the nested solver)
 __device__ inline int cone_exists(const Roche& R, double Px, double Py, double Pz, double s, double c,
                                   double cs, double sn, double t, int* nit = nullptr)
@@ -802,8 +861,11 @@ __device__ inline int cone_exists(const Roche& R, double Px, double Py, double P
     return -1;
 }
 
-// element_interval with the fast path; Rcal = sphere radius reproducing the
-// WD-centre contact (initial guesses only).  Whether an element is eclipsed
+// element_interval with the fast path; |Rcal| = sphere radius reproducing the
+// WD-centre contact (initial guesses only).  Rcal < 0 says that no line of
+// sight from this element can pass L1 within RAY_NEAR_L1 Rs (the setup lane
+// knows it for all WD and disc elements of a pair at once, l1_out_of_reach),
+// and the test for it is left out.  Whether an element is eclipsed
 // (cosD, the closest-approach potential, cone_exists, the final bound on both
 // contacts) is decided in FP64.  Trig: one atan2f and one acosf for the guess
 // angles, and two table reads (unit_dir) for the FP64 directions; with
@@ -823,6 +885,8 @@ __device__ inline bool element_interval_fast(const Roche& R, double Px, double P
         // theta_c = atan2(-uy, ux): closest approach of the line of sight to D
         const double cc = ux * iuxy, sc = -uy * iuxy;
         const double tc = s * uxy + uz * c;
+        const bool l1_reach = !(Rcal < 0.0);  // (tangency_may_pass_l1, once both contacts stand)
+        Rcal = fabs(Rcal);
         // the closest approach to D inside the lobe decides at once (one
         // potential, no gradient or Hessian); otherwise the cone search
         int ex;
@@ -888,7 +952,9 @@ __device__ inline bool element_interval_fast(const Roche& R, double Px, double P
                     tangency_pair(R, Px, Py, Pz, s, c, In, Out, nit ? nit + 1 : nullptr, hIn, hOut);
                     // both contacts within Dm of thc, as cos(th - thc) > cos Dm (below)
                     const double cin = In.cs * cc + In.sn * sc, cout = Out.cs * cc + Out.sn * sc;
-                    if (In.st == 1 && Out.st == 1 && In.th < Out.th && cin > cosD && cout > cosD) {
+                    if (In.st == 1 && Out.st == 1 && In.th < Out.th && cin > cosD && cout > cosD &&
+                        !(l1_reach && tangency_may_pass_l1(R, ux, uz, uxy2, s, c) &&
+                          (tangency_near_l1(R, Px, Py, Pz, s, c, In) || tangency_near_l1(R, Px, Py, Pz, s, c, Out)))) {
                         a = In.th * (1.0 / TWO_PI);
                         b = Out.th * (1.0 / TWO_PI);
                         return true;
@@ -931,7 +997,9 @@ __device__ inline bool element_interval_fast(const Roche& R, double Px, double P
                 // rotated cosines: no acos; the steps are clamped to 0.05 rad
                 // and the solve is short, so |th - thc| stays far below pi
                 const double cin = In.cs * cc + In.sn * sc, cout = Out.cs * cc + Out.sn * sc;
-                if (In.st == 1 && Out.st == 1 && In.th < Out.th && cin > cosD && cout > cosD) {
+                if (In.st == 1 && Out.st == 1 && In.th < Out.th && cin > cosD && cout > cosD &&
+                    !(l1_reach && tangency_may_pass_l1(R, ux, uz, uxy2, s, c) &&
+                          (tangency_near_l1(R, Px, Py, Pz, s, c, In) || tangency_near_l1(R, Px, Py, Pz, s, c, Out)))) {
                     a = In.th * (1.0 / TWO_PI);
                     b = Out.th * (1.0 / TWO_PI);
                     return true;
@@ -941,7 +1009,7 @@ __device__ inline bool element_interval_fast(const Roche& R, double Px, double P
 #endif  // LFG_TAB_START
     }
     if (fallback) *fallback = true;
-    return element_interval(R, Px, Py, Pz, s, c, Reff, a, b);
+    return element_interval<3>(R, Px, Py, Pz, s, c, Reff, a, b);
 }
 
 // findphi / findi with the same 2-D tangency Newton, nested solver fallback

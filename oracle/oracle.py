@@ -52,6 +52,7 @@ class Oracle:
         lib.lfo_findphi.argtypes = [ctypes.c_double, ctypes.c_double, _dp]
         lib.lfo_findi.argtypes = [ctypes.c_double, ctypes.c_double, _dp]
         lib.lfo_bspot.argtypes = [ctypes.c_double, ctypes.c_double, _dp]
+        lib.lfo_point_interval.argtypes = [ctypes.c_double, ctypes.c_double, _dp, _dp, _dp]
         lib.lfo_flux.argtypes = [_dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
                                  ctypes.c_int, _dp, _dp, _dp, _dp, _dp]
         lib.lfo_elements.argtypes = [_dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]
@@ -98,6 +99,13 @@ class Oracle:
         if st:
             raise ValueError("bspot failed (status %d)" % st)
         return tuple(out)
+
+    def point_interval(self, q, inc, P):
+        """lfo_point_interval: (eclipsed, a, b) of point P in phase (MODEL_SPEC 4.3)"""
+        P, pp = _f(P)
+        a, b = ctypes.c_double(), ctypes.c_double()
+        ecl = self.lib.lfo_point_interval(float(q), float(inc), pp, ctypes.byref(a), ctypes.byref(b))
+        return bool(ecl), a.value, b.value
 
     def wdphases(self, q, inc, r1, ntheta=10):
         p3, p4 = ctypes.c_double(), ctypes.c_double()

@@ -102,6 +102,45 @@ def _elements_gpu(pars):
     return [t.cpu().numpy() for t in (st, a, b, wg, don, geo)]
 
 
+# what the oracle's geo record (lfo_elements) and the device's (lfg_device.hpp
+# enum Geo) both hold: oracle slot -> device slot.  The oracle's stream
+# velocity and donor norm have no device counterpart (the element kernels
+# compute neither), and the device's other slots are inputs or derived
+# (sin i, cos i, the strip's direction, the beaming normal).
+GEO_PAIRS = {"xl1": (0, 4), "pl1": (1, 5), "inc": (2, 10), "rwd_a": (3, 11), "rdisc_a": (4, 12), "bs_x": (5, 16),
+             "bs_y": (6, 17), "upk": (9, 21), "umax": (10, 22), "l": (11, 20), "bden": (12, 31), "reff": (14, 13),
+             "lnpk": (15, 23)}
+GEO_TOL = 1e-12
+
+
+def assert_geo_matches(geo, ogeo, label=""):
+    """the geometry both sides export (x_L1, Phi(L1), inclination, radii, the
+    stream's impact point, the strip's profile constants, the beaming
+    denominator) to GEO_TOL, relative, or absolute for values below 1.
+
+    The inclination alone has a second rule.  The eclipse is symmetric in
+    cos i, so dphi fixes cos^2 i, and next to 90 degrees the inclination
+    itself only as well as d(cos^2 i) / (2 cos i): two solves of the egress
+    phase to 1e-13 rad differ by 2e-9 degrees at i = 89.965.  There the
+    comparison is on cos^2 i, at GEO_TOL / 10 (which is the tighter rule
+    wherever cos i > 0.05).
+    The beaming denominator is fis + (1 - fis) max(0, |sin t| sin i + cos t
+    cos i): it follows cos i with a slope of at most 1 + cot i < 2 (i > 45
+    degrees wherever the WD is eclipsed), so it may differ by twice the two
+    sides' difference in cos i beside GEO_TOL."""
+    bad = []
+    ci = [np.cos(np.radians(g[k])) for g, k in ((geo, GEO_PAIRS["inc"][1]), (ogeo, GEO_PAIRS["inc"][0]))]
+    for name, (ko, kd) in GEO_PAIRS.items():
+        ok = abs(geo[kd] - ogeo[ko]) <= GEO_TOL * max(1.0, abs(ogeo[ko]))
+        if name == "inc" and not ok:
+            ok = abs(ci[0] ** 2 - ci[1] ** 2) <= 0.1 * GEO_TOL
+        if name == "bden" and not ok:
+            ok = abs(geo[kd] - ogeo[ko]) <= GEO_TOL + 2.0 * abs(ci[0] - ci[1])
+        if not ok:
+            bad.append((name, float(geo[kd]), float(ogeo[ko])))
+    assert not bad, (label, bad)
+
+
 @pytest.mark.parametrize("pars", [TRUTH18, ECL1, TRUTH14])
 def test_element_tables(oracle, pars):
     st, a, b, wg, don, geo = _elements_gpu(pars)
@@ -113,6 +152,7 @@ def test_element_tables(oracle, pars):
     assert np.max(np.abs(b[0][ecl] - ob[ecl])) < PHASE_ATOL
     np.testing.assert_allclose(wg[0], ow, rtol=1e-12)
     np.testing.assert_allclose(don[0], odon, rtol=1e-9, atol=1e-14)
+    assert_geo_matches(geo[0], ogeo)
 
 
 def _grazing_sets():
