@@ -16,6 +16,35 @@
  * `status` and turn into NaN flux / -inf ln_like, exactly as the reference
  * turns an lfit exception into NaN (CVModel.py:137-144) and -inf
  * (CVModel.py:163-171, model.py:485-493).
+ *
+ * The memory contract (tests/test_gpu_abi_guard.py pins it with guarded
+ * buffers):
+ *   - a call writes its outputs, of exactly the shapes stated here, and its
+ *     scratch within the first ws_bytes bytes, and nothing else; `const`
+ *     inputs are left alone;
+ *   - scratch (`ws`) must be aligned to 256 bytes, and to no more.  It may
+ *     hold anything on entry (no call reads a scratch slot before writing it)
+ *     except where a call is documented to continue from the state another
+ *     call left there (the speculative stretch calls);
+ *   - ws_bytes below what the call needs is refused with LFG_E_WORKSPACE
+ *     (LFG_E_ARGS by the GP posterior calls) before anything is launched:
+ *     no output and no scratch byte is written;
+ *   - every output element is written, with the value stated for failed sets
+ *     and rejected walkers (NaN, -inf), unless its entry point says here that
+ *     it is left unwritten.
+ * Which size function a call's scratch comes from:
+ *   lfg_flux, lfg_lnlike, lfg_elements          lfg_workspace_size(W, 1)
+ *   lfg_lnprob, lfg_lnprior, lfg_lnprob_timed   lfg_workspace_size_tree(W, tree)
+ *   every lfg_stretch_* call that takes one     lfg_workspace_size_tree(W/2, tree),
+ *       whatever the shard (n <= W/2 walkers); one buffer per rank serves the
+ *       whole family
+ *   lfg_pt_swap, lfg_gp_predict, lfg_gp_sample, lfg_gp_predict_tree,
+ *   lfg_component                               their own size functions
+ * lfg_workspace_size_tree includes the speculative candidates, which only
+ * lfg_stretch_step_half_spec, _step_shard_spec, _accept_regen_spec and
+ * _step_shard_fold keep: the other tree calls work in the first
+ * lfg_workspace_size(n, tree->E) bytes for their n walkers when the tree is a
+ * chi^2 tree, and are refused only below that.
  */
 #ifndef LFG_H
 #define LFG_H
@@ -123,6 +152,8 @@ size_t lfg_workspace_size(int W, int E);
  *   comps  [dev] nullable, 4 x W x N: white dwarf, disc, bright spot, donor
  *          (lfit's cv.ywd, cv.yd, cv.ys, cv.yrs; CVModel.py:155)
  *   status [dev] W (LFG_ST_*)
+ * The flux (and comps) row of a set whose status is not LFG_ST_OK is NaN.
+ * N = 0 writes status alone.
  */
 int lfg_flux(const double* pars, int W, int P, const double* x,
              const double* w, int N, int nsub, double* flux, double* comps,
@@ -136,7 +167,8 @@ int lfg_flux(const double* pars, int W, int P, const double* x,
  * applied (lfg_lnprob adds the priors through a tree).
  *   pars, x, w, N, nsub, status: as lfg_flux
  *   y, ye   [dev] N data points and errors
- *   lnlike  [dev] W (-inf where status != LFG_ST_OK)
+ *   lnlike  [dev] W (-inf where status != LFG_ST_OK; the empty sum, 0, for
+ *           N = 0 on either kernel layout)
  * Workspace: lfg_workspace_size(W, 1).
  */
 int lfg_lnlike(const double* pars, int W, int P, const double* x,
@@ -151,7 +183,12 @@ int lfg_lnlike(const double* pars, int W, int P, const double* x,
  * (CVModel.py:157-191), fused: no flux array is materialised.
  *   walkers  [dev] W x ndim
  *   lnp      [dev] W
- *   lnlike_e [dev] nullable, W x E per-eclipse ln_like
+ *   lnlike_e [dev] nullable, W x E per-eclipse ln_like.  Every element is
+ *            written and none is NaN: for a walker whose ln_prob is -inf
+ *            (its prior, a non-finite coordinate or a failed model) an entry
+ *            is -inf or, where the model was still evaluated, that eclipse's
+ *            ln_like; lnp alone says whether the walker counts
+ * Workspace: lfg_workspace_size_tree(W, tree).
  */
 int lfg_lnprob(const double* walkers, int W, const lfg_tree* tree,
                double* lnp, double* lnlike_e, void* ws, size_t ws_bytes,
@@ -171,7 +208,11 @@ int lfg_lnprior(const double* walkers, int W, const lfg_tree* tree,
  * White-box access to the element tables of MODEL_SPEC.md section 5 for W
  * parameter sets (tests): a, b, wgt [dev] W x LFG_NEL eclipse intervals
  * (phase) and weights; donor [dev] W x LFG_NDONOR x 3; geo [dev] W x LFG_NGEO;
- * status [dev] W.
+ * status [dev] W.  Each output is nullable.  The a, b, wgt and donor rows of
+ * a set whose status is not LFG_ST_OK are left unwritten; the geo slots that
+ * no call without a tree defines (the stream's velocity at the bright spot,
+ * slots 18 and 19, and the GP likelihood's, 41 to 47) and those a failed set
+ * did not reach are 0.
  */
 int lfg_elements(const double* pars, int W, int P, double* a, double* b,
                  double* wgt, double* donor, double* geo, int* status,
@@ -183,7 +224,9 @@ int lfg_elements(const double* pars, int W, int P, double* a, double* b,
  *   op 1 findphi(q = a[i], inc = b[i])     -> out[i]
  *   op 2 findi(q = a[i], dphi = b[i])      -> out[i]
  *   op 3 bspot(q = a[i], rad = b[i])       -> out[4i .. 4i+3] = x, y, vx, vy
- * a, b, out, status are [dev]; status[i] = LFG_ST_*.
+ * a, b, status are [dev] n (b unused by op 0); out [dev] is n doubles for
+ * ops 0-2 and 4 n doubles for op 3; status[i] = LFG_ST_*, and the out entries
+ * of a row whose status is not LFG_ST_OK are NaN.
  */
 int lfg_roche(int op, const double* a, const double* b, int n, double* out,
               int* status, void* stream);
@@ -286,6 +329,7 @@ int lfg_stretch_step_half_spec(double* pos, double* lnp, int W, int half,
  * walkers lo .. lo+n-1 of half `half` inside k_setup (same draws as
  * lfg_stretch_propose's lanes lo .. lo+n-1) and writes their ln_prob to
  * lnp_new [dev] n; q [dev] n x ndim and zfac [dev] n receive the proposals.
+ * These are exactly n rows: nothing outside the shard is written.
  * After the caller has gathered every rank's lnp_new into the W/2 vector,
  * lfg_stretch_accept_regen applies the Metropolis step to the whole half,
  * re-forming each proposal from its draws (bit-identical to k_propose), so
@@ -452,7 +496,8 @@ int lfg_pt_swap(const double* pos_in, double* pos_out, double* lnl,
 /*
  * Batched trm.roche.wdphases(q, iangle, r1, ntheta) (CVModel.py:564): third
  * and fourth contact phases of a sphere of radius r1 at the white dwarf.
- * q, inc (degrees), r1, phi3, phi4, status: [dev] n.
+ * q, inc (degrees), r1, phi3, phi4, status: [dev] n.  phi3[i] and phi4[i]
+ * of a row whose status is not LFG_ST_OK are NaN.
  */
 int lfg_wdphases(const double* q, const double* inc, const double* r1, int n,
                  int ntheta, double* phi3, double* phi4, int* status,
@@ -550,8 +595,9 @@ int lfg_gp_predict_tree(const double* walkers, int W, const lfg_tree* tree,
  * q, inc [dev] W; grids: disc n1 rings x n2 azimuths, spot n1 strip
  * elements, donor n1 bands x n2 azimuths (the WD grid is fixed, 400 tiles);
  * x, w [dev] N phases (used as given: no phi0) and exposure half-widths
- * (w = NULL: points); out [dev] W x N; status [dev] W.  Scratch ws of at
- * least lfg_component_workspace_size(kind, W, n1, n2) bytes.
+ * (w = NULL: points); out [dev] W x N; status [dev] W (LFG_ST_*); the out
+ * row of a set whose status is not LFG_ST_OK is NaN.  Scratch ws of at least
+ * lfg_component_workspace_size(kind, W, n1, n2) bytes.
  */
 size_t lfg_component_workspace_size(int kind, int W, int n1, int n2);
 int lfg_component(int kind, const double* cpars, int ncp, const double* q,

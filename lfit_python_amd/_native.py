@@ -296,16 +296,38 @@ def stream_ptr(device=None):
 
 
 class Workspace:
-    """Grow-only scratch buffer for the lfg_* entry points (one per device)."""
+    """Grow-only scratch buffers for the lfg_* entry points, one per device
+    and stream.
 
-    _pool = {}
+    The rule: get() hands out the buffer of the stream that is current on
+    `device` when it is called, and the caller launches on that same stream
+    (stream_ptr).  Two streams therefore never share scratch, so calls made
+    under different streams need no ordering between them, and calls on one
+    stream are ordered by the stream itself.  When a request outgrows the
+    stream's buffer, the old one is retired, not dropped: it stays alive,
+    paired with an event recorded on its stream at that moment, until the
+    event has completed, i.e. until every kernel queued on it has run.
+    (torch hands out pooled streams, at most a few dozen per device, so the
+    pool stays small.)"""
+
+    _pool = {}     # (device index, stream handle) -> buffer
+    _retired = []  # (event, buffer) of outgrown buffers whose queued work may not have finished
 
     @classmethod
     def get(cls, nbytes, device):
         import torch
-        key = str(device)
+        device = torch.device(device)
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        stream = torch.cuda.current_stream(index)
+        key = (index, stream.cuda_stream)
+        cls._retired = [(e, b) for e, b in cls._retired if not e.query()]
         buf = cls._pool.get(key)
         if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+            if buf is not None:
+                done = torch.cuda.Event()
+                done.record(stream)
+                cls._retired.append((done, buf))
+            with torch.cuda.stream(stream):  # allocated for this stream, whatever device is current
+                buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=torch.device("cuda", index))
             cls._pool[key] = buf
         return buf

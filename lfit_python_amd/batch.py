@@ -144,7 +144,9 @@ def prior_consts(tree):
 class LnProbEvaluator:
     """Device-resident ln_prob for a compiled tree (one per GPU / stream)."""
 
-    def __init__(self, tree, device=None, max_walkers=0):
+    def __init__(self, tree, device=None, max_walkers=0, scratch=None):
+        """scratch: an optional caller-owned uint8 device tensor to work in
+        (see use_scratch) instead of one the evaluator allocates."""
         import torch
         _native.require_gpu()
         self.L = _native.lib()
@@ -164,21 +166,51 @@ class LnProbEvaluator:
             self._buf.update(gp_gather=t(tree.gp_gather.reshape(-1), i32),
                              gp_base=t(self._gp_base(tree), f64),
                              gp_ecl=t(tree.gp_ecl.reshape(-1), i32))
-        b = self._buf
+        self._bind()
+        self._ws = None
+        self._ws_walkers = 0
+        self._ws_fixed = False
+        self._spec_key = None  # step_half(spec=True): what the workspace's candidates are for
+        # bumped whenever the workspace is reallocated: a captured HIP graph
+        # holds the old pointer (sampler.EnsembleSampler re-captures on change)
+        self.generation = 0
+        if scratch is not None:
+            self.use_scratch(scratch)
+        if max_walkers:
+            self._ensure(max_walkers)
+
+    def _bind(self):
+        """(Re)build the lfg_tree from the device tensors in self._buf."""
+        tree, b = self.tree, self._buf
         p = lambda k: ctypes.c_void_p(b[k].data_ptr()) if k in b else None
         self.ctree = _native.LfgTree(
             tree.E, tree.ndim, tree.nsub, tree.max_n, p('gather'), p('npars'), p('consts'),
             p('off'), p('x'), p('y'), p('ye'), p('w'), p('prior_type'), p('prior_p1'),
             p('prior_p2'), p('prior_norm'), int(tree.roche_priors), int(tree.gp),
             p('gp_gather'), p('gp_base'), p('gp_ecl'), int(tree.fixed_invalid), p('prior_c'))
-        self._ws = None
-        self._ws_walkers = 0
-        self._spec_key = None  # step_half(spec=True): what the workspace's candidates are for
-        # bumped whenever the workspace is reallocated: a captured HIP graph
-        # holds the old pointer (sampler.EnsembleSampler re-captures on change)
-        self.generation = 0
-        if max_walkers:
-            self._ensure(max_walkers)
+
+    def relocate(self, place):
+        """Move the tree's device arrays: place(name, tensor) returns the
+        tensor to use from now on for array `name` (same dtype, shape and
+        contents, e.g. a copy in memory the caller watches); the lfg_tree is
+        rebuilt over the returned tensors."""
+        for k in sorted(self._buf):
+            self._buf[k] = place(k, self._buf[k])
+        self._bind()
+        self._spec_key = None
+
+    def arrays(self):
+        """name -> device tensor of the tree's arrays (read-only use)"""
+        return dict(self._buf)
+
+    def use_scratch(self, scratch):
+        """Work in the caller's uint8 device tensor from now on: every call
+        passes exactly this tensor (its numel() as ws_bytes) and the evaluator
+        never allocates; a call that needs more fails with LFG_E_WORKSPACE."""
+        self._ws = scratch
+        self._ws_fixed = True
+        self._spec_key = None
+        self.generation += 1
 
     def _gp_base(self, tree):
         """[E, 4] q, dphi, rwd, dist_cp of the changepoint cache; a cache the
@@ -196,6 +228,8 @@ class LnProbEvaluator:
 
     def _ensure(self, W):
         import torch
+        if self._ws_fixed:
+            return
         if W > self._ws_walkers:
             nbytes = self.L.lfg_workspace_size_tree(W, ctypes.byref(self.ctree))
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)

@@ -2518,7 +2518,10 @@ __global__ __launch_bounds__(LIKE_THREADS, LIKE_MINW) void k_lnlike(LikeArgs L)
         __syncthreads();
         if (tid == 0) {
             double tot = 0.0;
-            for (int i = 0; i < nw; ++i) tot += red[1][i];
+            // an eclipse without points ran no tile: red[1] still holds the
+            // prologue's partial sums, and chi^2 is the empty sum
+            if (n > 0)
+                for (int i = 0; i < nw; ++i) tot += red[1][i];
             L.lle[pair] = -0.5 * tot;
         }
         finish_walker(L, pair, tid, acc1, sq, sacc1, sflag);
@@ -6096,6 +6099,10 @@ int lfg_elements(const double* pars, int W, int P, double* a, double* b, double*
     if (!wsp || ws_bytes < ws.total) return LFG_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SetupArgs S = setup_args_flat(pars, W, P, ws);
+    // k_setup writes the slots a set's model defines and stops at a failure:
+    // the rest of the record is copied out below, so it must not be whatever
+    // the scratch held (lfg.h: those slots are 0)
+    if (geo && hipMemsetAsync(ws.geo, 0, size_t(W) * LFG_NGEO * sizeof(double), st) != hipSuccess) return LFG_E_LAUNCH;
     int rc = run_front(S, ws, st, nullptr, true);  // the white-box tables come from k_elements
     if (rc) return rc;
     if (a || b || wgt || donor) {

@@ -688,6 +688,13 @@ def test_chunked_production_keeps_device_memory_flat(tmp_path):
     S = sampler.EnsembleSampler(W, t.ndim, ev, seed=5)
     pos, lnp, st = S.run_mcmc(init, 2, storechain=False)
     assert S.last_run() is None
+    # Earlier tests leave samplers in reference cycles (a half_timer closure
+    # holds its sampler and evaluator: 1.3 MB of workspace); when the
+    # collector frees one is a matter of how many objects the session has
+    # made, and a collection between two of the readings below is not a chunk
+    # leaving the device.  Collect first: the readings count this test's own.
+    import gc
+    gc.collect()
     used = []
     for k in range(6):
         S.run_mcmc(None, 10, storechain=True)
