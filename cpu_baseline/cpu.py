@@ -23,7 +23,8 @@ def build(out=None, march="x86-64-v3", extra=()):
     out = out or LIB_PATH
     cmd = ["g++", "-O3", "-march=%s" % march, "-fopenmp", "-std=c++17", "-fPIC", "-shared"] + list(extra) + [
            "-I", HERE, "-I", os.path.join(HERE, "shim"), "-I", os.path.join(ROOT, "lfit_python_amd", "csrc"),
-           "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp")]
+           "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp"),
+           os.path.join(HERE, "lfg_cpu_physpar.cpp")]
     subprocess.run(cmd, check=True)
     return out
 
@@ -131,6 +132,29 @@ class CpuPort:
         if rc != 0:
             raise ValueError("lfg_cpu_gp_predict: code %d" % rc)
         return mean, var, st
+
+    def physpar(self, q, dphi, rwd, twd, p, tables, ld=1, n=None, nthreads=0):
+        """lfg_cpu_physpar: (table [n, 10], model [n], status [n]).  tables:
+        a lfit_python_amd.physpar.MRTables; q, dphi and rwd are read at
+        element i * ld (n rows; default: their length with ld = 1)."""
+        from lfit_python_amd import _native
+        q, dphi, rwd, twd, p = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (q, dphi, rwd, twd, p))
+        n = twd.size if n is None else int(n)
+        assert p.size >= n and twd.size >= n and all(a.size == 0 or a.size > (n - 1) * ld for a in (q, dphi, rwd))
+        out = np.empty((10, n))
+        model = np.empty(n, dtype=np.int32)
+        st = np.empty(n, dtype=np.int32)
+        f = self.lib.lfg_cpu_physpar
+        f.restype = ctypes.c_int
+        f.argtypes = [_dp, _dp, _dp, ctypes.c_size_t, _dp, _dp, ctypes.c_int, ctypes.POINTER(_native.LfgMrTables),
+                      _dp, _ip, _ip, ctypes.c_int]
+        T = tables.host_struct()
+        rc = f(q.ctypes.data_as(_dp), dphi.ctypes.data_as(_dp), rwd.ctypes.data_as(_dp), int(ld),
+               twd.ctypes.data_as(_dp), p.ctypes.data_as(_dp), n, ctypes.byref(T), out.ctypes.data_as(_dp),
+               model.ctypes.data_as(_ip), st.ctypes.data_as(_ip), int(nthreads))
+        if rc != 0:
+            raise ValueError("lfg_cpu_physpar: code %d" % rc)
+        return np.ascontiguousarray(out.T), model, st
 
     def lnprob(self, walkers, tree, nthreads=0):
         """lfg_cpu_lnprob through a struct lfg_tree of host arrays"""

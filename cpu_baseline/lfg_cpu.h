@@ -11,6 +11,7 @@
 #define LFG_CPU_H
 
 #include "lfg.h"
+#include "lfg_physpar.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -38,6 +39,13 @@ int lfg_cpu_gp_predict(const double* x, const double* ye, const int* obs,
                        const double* res, int W, int n, const double* hyp,
                        const double* blocks, int nb, double* mean, double* var,
                        int* status, int nthreads);
+
+/* lfg_physpar's twin (include/lfg_physpar.h; calcPhysicalParams.py solve()):
+ * the same arguments on host pointers, the tables' arrays included */
+int lfg_cpu_physpar(const double* q, const double* dphi, const double* rwd,
+                    size_t ld, const double* twd, const double* p, int n,
+                    const lfg_mr_tables* tab, double* out, int* model,
+                    int* status, int nthreads);
 
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */

@@ -26,14 +26,16 @@ if os.environ.get("LFG_LIB"):
     LOAD_PATH = os.environ["LFG_LIB"]
 SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "lfg_components.hip"),
            os.path.join(_HERE, "csrc", "lfg_pt.hip"),  # lfg_pt.hip: the parallel-tempering kernels, a unit of their own
-           os.path.join(_HERE, "csrc", "lfg_gp_predict.hip")]  # the GP smoother and conditional sampler
+           os.path.join(_HERE, "csrc", "lfg_gp_predict.hip"),  # the GP smoother and conditional sampler
+           os.path.join(_HERE, "csrc", "lfg_physpar.hip")]  # physical parameters from chain rows (lfg_physpar.h)
 # k_pair's fold and LONG instantiations: lfg.hip again, compiled on its own
 # without machine LICM (the reason: lfg.hip, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
 SPLIT_FLAGS = ["-mllvm", "-disable-machine-licm"]
 # every header a unit can include: whatever csrc/ holds, and the C ABI
 HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
-                 if f.endswith((".hpp", ".h"))) + [os.path.join(REPO, "include", "lfg.h")]
+                 if f.endswith((".hpp", ".h"))) + [os.path.join(REPO, "include", "lfg.h"),
+                                                   os.path.join(REPO, "include", "lfg_physpar.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 
@@ -51,6 +53,9 @@ STATUS_TEXT = {
     4: "the gas stream does not reach the disc radius",
     5: "non-finite or wrong-length parameter vector",
 }
+# lfg_physpar's rows (include/lfg_physpar.h) add one code
+STATUS_TEXT_PHYSPAR = {**STATUS_TEXT, 5: "non-finite input, or rwd, twd or p not positive",
+                       6: "no mass-radius relation brackets a white-dwarf mass"}
 
 
 class LfgTree(ctypes.Structure):
@@ -84,6 +89,23 @@ EXPORTS = ("lfg_workspace_size", "lfg_workspace_size_tree", "lfg_flux", "lfg_lnl
            "lfg_pt_workspace_size", "lfg_pt_propose", "lfg_pt_accept", "lfg_pt_swap",
            "lfg_gp_predict_workspace_size", "lfg_gp_predict", "lfg_gp_sample_workspace_size", "lfg_gp_sample",
            "lfg_gp_predict_tree_workspace_size", "lfg_gp_predict_tree")
+
+
+# include/lfg_physpar.h: a set of its own (EXPORTS is include/lfg.h's, and pinned to it)
+EXPORTS_PHYSPAR = ("lfg_physpar", "lfg_physpar_lanes")
+MR_NWOOD, MR_MAX_KNOTS, MR_MAX_DOUBLES = 7, 32, 8192  # LFG_MR_* (include/lfg_physpar.h)
+
+
+class LfgMrTables(ctypes.Structure):
+    """ctypes mirror of struct lfg_mr_tables (include/lfg_physpar.h)."""
+    _fields_ = [
+        ("wood_t", ctypes.c_void_p), ("wood_r", ctypes.c_void_p), ("wood_off", ctypes.c_int * (MR_NWOOD + 1)),
+        ("wood_card", ctypes.c_void_p), ("ham_m", ctypes.c_void_p), ("ham_r", ctypes.c_void_p),
+        ("n_ham", ctypes.c_int),
+        ("pan_tx", ctypes.c_void_p), ("pan_ty", ctypes.c_void_p), ("pan_c", ctypes.c_void_p),
+        ("pan_nx", ctypes.c_int), ("pan_ny", ctypes.c_int),
+        ("G", ctypes.c_double), ("GMsun", ctypes.c_double), ("Rsun", ctypes.c_double), ("day", ctypes.c_double),
+    ]
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -271,6 +293,10 @@ def lib():
         L.lfg_version.argtypes = []
         L.lfg_layout.restype = ip
         L.lfg_layout.argtypes = [ctypes.POINTER(LfgTree)]
+        L.lfg_physpar.restype = ip
+        L.lfg_physpar.argtypes = [vp, vp, vp, sz, vp, vp, ip, ctypes.POINTER(LfgMrTables), vp, vp, vp, vp]
+        L.lfg_physpar_lanes.restype = ip
+        L.lfg_physpar_lanes.argtypes = []
         if hasattr(L, "lfg_set_layout"):  # (older experiment builds lack it)
             L.lfg_set_layout.restype = ip
             L.lfg_set_layout.argtypes = [ip]

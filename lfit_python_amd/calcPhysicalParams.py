@@ -1,0 +1,70 @@
+"""python -m lfit_python_amd.calcPhysicalParams file twd e_twd p e_p [--thin N] [--flat N] --dir DIR
+
+The reference's calcPhysicalParams.py script on the device: reads a chain
+file, draws the white-dwarf temperature and the period per sample, solves
+every sample (lfit_python_amd.physpar) and writes physicalparams.log and
+physicalparams_summary.log into the working directory.  The arguments and
+the printed messages are the reference's; it makes no plots, and --nthreads
+is accepted and ignored (there is no process pool).  --seed seeds the draws
+(the reference's are unseeded).
+"""
+import argparse
+import sys
+
+import numpy as np
+
+from . import mcmc_utils, physpar
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="Calculate physical parameters from MCMC chain of LFIT parameters")
+    parser.add_argument("file", help="chain_prod file from mcmcfit run")
+    parser.add_argument("twd", type=float, help="white dwarf temperature (K)")
+    parser.add_argument("e_twd", type=float, help="error on wd temp")
+    parser.add_argument("p", type=float, help="orbital period (days)")
+    parser.add_argument("e_p", type=float, help="error on period")
+    parser.add_argument("--thin", "-t", type=int, default=1, help="amount to thin MCMC chain by")
+    parser.add_argument("--nthreads", "-n", type=int, default=6, help="ignored: the rows are solved on the device")
+    parser.add_argument("--flat", "-f", type=int, default=0, help="Factor of thinning if flattened chain used")
+    parser.add_argument("--dir", "-d", required=True, help="directory with WD models")
+    parser.add_argument("--seed", type=int, default=0, help="seed of the twd and p draws")
+    args = parser.parse_args(argv)
+
+    print("baseDir (must contain WD model directories): {}".format(args.dir))
+    tables = physpar.load_mr_tables(args.dir)
+    print("Reading chain file...")
+    with open(args.file, "r") as fh:
+        names = fh.readline().strip().split(" ")[1:]
+    if args.flat > 0:
+        # a flattened chain: the header's names after its first word label the columns
+        # (the reference's readflatchain would read the header line as data; it is left out here)
+        fchain = np.loadtxt(args.file, skiprows=1, ndmin=2)
+        nobjects = int((args.flat * len(fchain)) / args.thin)
+        fchain = fchain[:nobjects]
+    else:
+        chain = mcmc_utils.readchain(args.file)
+        fchain = mcmc_utils.flatchain(chain, chain.shape[2], thin=args.thin)
+    print("Done!")
+    fchain = np.ascontiguousarray(fchain, dtype=np.float64)
+    cols = {k: fchain[:, names.index(k)] for k in ("q_core", "dphi_core", "rwd_core")}
+    n = len(fchain)
+    print("The chain contains {} samples".format(n))
+    print("Means; ")
+    print("  q: {:.3f}".format(np.mean(cols["q_core"])))
+    print("  dphi: {:.3f}".format(np.mean(cols["dphi_core"])))
+    print("  rwd: {:.3f}".format(np.mean(cols["rwd_core"])))
+
+    print("Getting solutions for each step of the MCMC chain...")
+    table, model, status = physpar.from_chain(fchain, names[:fchain.shape[1]], args.twd, args.e_twd, args.p, args.e_p,
+                                              tables, seed=args.seed)
+    print("Writing out results...")
+    stats = physpar.summary(table, status)
+    print("Found solutions for %d percent of samples in MCMC chain" % (100 * float(stats["solved"]) / float(n)))
+    physpar.write_results(table, status, ".", stats=stats)
+    for line in physpar.summary_lines(stats):
+        print(line)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
