@@ -24,7 +24,7 @@ def build(out=None, march="x86-64-v3", extra=()):
     cmd = ["g++", "-O3", "-march=%s" % march, "-fopenmp", "-std=c++17", "-fPIC", "-shared"] + list(extra) + [
            "-I", HERE, "-I", os.path.join(HERE, "shim"), "-I", os.path.join(ROOT, "lfit_python_amd", "csrc"),
            "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp"),
-           os.path.join(HERE, "lfg_cpu_physpar.cpp")]
+           os.path.join(HERE, "lfg_cpu_physpar.cpp"), os.path.join(HERE, "lfg_cpu_wd.cpp")]
     subprocess.run(cmd, check=True)
     return out
 
@@ -155,6 +155,30 @@ class CpuPort:
         if rc != 0:
             raise ValueError("lfg_cpu_physpar: code %d" % rc)
         return np.ascontiguousarray(out.T), model, st
+
+    def wd_lnprob(self, theta, model, ld=None, n=None, nthreads=0):
+        """lfg_cpu_wd_lnprob: (lnp [n], lnlike [n], mags [n, B], status [n]).
+        model: a lfit_python_amd.wdparams.WDModel; theta [n, ld], or flat with
+        row i at element i * ld."""
+        from lfit_python_amd import _native
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        if ld is None:
+            n, ld = th.shape
+        th = th.reshape(-1)
+        n = int(n)
+        assert n == 0 or th.size >= (n - 1) * ld + 4
+        lnp, ll, st = np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)
+        mags = np.empty((model.B, n))
+        f = self.lib.lfg_cpu_wd_lnprob
+        f.restype = ctypes.c_int
+        f.argtypes = [_dp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_native.LfgWdModel), _dp, _dp, _dp, _ip,
+                      ctypes.c_int]
+        M = model.host_struct()
+        rc = f(th.ctypes.data_as(_dp), int(ld), n, ctypes.byref(M), lnp.ctypes.data_as(_dp), ll.ctypes.data_as(_dp),
+               mags.ctypes.data_as(_dp), st.ctypes.data_as(_ip), int(nthreads))
+        if rc != 0:
+            raise ValueError("lfg_cpu_wd_lnprob: code %d" % rc)
+        return lnp, ll, np.ascontiguousarray(mags.T), st
 
     def lnprob(self, walkers, tree, nthreads=0):
         """lfg_cpu_lnprob through a struct lfg_tree of host arrays"""

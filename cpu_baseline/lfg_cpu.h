@@ -12,6 +12,7 @@
 
 #include "lfg.h"
 #include "lfg_physpar.h"
+#include "lfg_wd.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -46,6 +47,12 @@ int lfg_cpu_physpar(const double* q, const double* dphi, const double* rwd,
                     size_t ld, const double* twd, const double* p, int n,
                     const lfg_mr_tables* tab, double* out, int* model,
                     int* status, int nthreads);
+
+/* lfg_wd_lnprob's twin (include/lfg_wd.h; wdparams_new.py ln_prob): the same
+ * arguments on host pointers, the model's arrays included */
+int lfg_cpu_wd_lnprob(const double* theta, size_t ld, int n,
+                      const lfg_wd_model* model, double* lnp, double* lnlike,
+                      double* mags, int* status, int nthreads);
 
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */

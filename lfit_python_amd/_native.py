@@ -27,7 +27,8 @@ if os.environ.get("LFG_LIB"):
 SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "lfg_components.hip"),
            os.path.join(_HERE, "csrc", "lfg_pt.hip"),  # lfg_pt.hip: the parallel-tempering kernels, a unit of their own
            os.path.join(_HERE, "csrc", "lfg_gp_predict.hip"),  # the GP smoother and conditional sampler
-           os.path.join(_HERE, "csrc", "lfg_physpar.hip")]  # physical parameters from chain rows (lfg_physpar.h)
+           os.path.join(_HERE, "csrc", "lfg_physpar.hip"),  # physical parameters from chain rows (lfg_physpar.h)
+           os.path.join(_HERE, "csrc", "lfg_wd.hip")]  # the white-dwarf atmosphere fit (lfg_wd.h)
 # k_pair's fold and LONG instantiations: lfg.hip again, compiled on its own
 # without machine LICM (the reason: lfg.hip, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -35,7 +36,8 @@ SPLIT_FLAGS = ["-mllvm", "-disable-machine-licm"]
 # every header a unit can include: whatever csrc/ holds, and the C ABI
 HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
                  if f.endswith((".hpp", ".h"))) + [os.path.join(REPO, "include", "lfg.h"),
-                                                   os.path.join(REPO, "include", "lfg_physpar.h")]
+                                                   os.path.join(REPO, "include", "lfg_physpar.h"),
+                                                   os.path.join(REPO, "include", "lfg_wd.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 
@@ -105,6 +107,27 @@ class LfgMrTables(ctypes.Structure):
         ("pan_tx", ctypes.c_void_p), ("pan_ty", ctypes.c_void_p), ("pan_c", ctypes.c_void_p),
         ("pan_nx", ctypes.c_int), ("pan_ny", ctypes.c_int),
         ("G", ctypes.c_double), ("GMsun", ctypes.c_double), ("Rsun", ctypes.c_double), ("day", ctypes.c_double),
+    ]
+
+
+# include/lfg_wd.h: a set of its own as well
+EXPORTS_WD = ("lfg_wd_lnprob", "lfg_wd_step_half")
+WD_NPAR, WD_MAX_BANDS, WD_MAX_KNOTS = 4, 8, 128  # LFG_WD_* (include/lfg_wd.h)
+
+
+class LfgWdModel(ctypes.Structure):
+    """ctypes mirror of struct lfg_wd_model (include/lfg_wd.h)."""
+    _fields_ = [
+        ("B", ctypes.c_int), ("nx", ctypes.c_int), ("ny", ctypes.c_int),
+        ("tx", ctypes.c_void_p), ("ty", ctypes.c_void_p), ("c", ctypes.c_void_p),
+        ("cnx", ctypes.c_int * WD_MAX_BANDS), ("cny", ctypes.c_int * WD_MAX_BANDS),
+        ("ctx", ctypes.c_void_p * WD_MAX_BANDS), ("cty", ctypes.c_void_p * WD_MAX_BANDS),
+        ("cc", ctypes.c_void_p * WD_MAX_BANDS),
+        ("k", ctypes.c_double * WD_MAX_BANDS), ("mag", ctypes.c_double * WD_MAX_BANDS),
+        ("err", ctypes.c_double * WD_MAX_BANDS), ("lnnorm", ctypes.c_double),
+        ("prior_type", ctypes.c_int * WD_NPAR), ("prior_p1", ctypes.c_double * WD_NPAR),
+        ("prior_p2", ctypes.c_double * WD_NPAR), ("prior_c0", ctypes.c_double * WD_NPAR),
+        ("prior_c1", ctypes.c_double * WD_NPAR),
     ]
 
 
@@ -297,6 +320,11 @@ def lib():
         L.lfg_physpar.argtypes = [vp, vp, vp, sz, vp, vp, ip, ctypes.POINTER(LfgMrTables), vp, vp, vp, vp]
         L.lfg_physpar_lanes.restype = ip
         L.lfg_physpar_lanes.argtypes = []
+        L.lfg_wd_lnprob.restype = ip
+        L.lfg_wd_lnprob.argtypes = [vp, sz, ip, ctypes.POINTER(LfgWdModel), vp, vp, vp, vp, vp]
+        L.lfg_wd_step_half.restype = ip
+        L.lfg_wd_step_half.argtypes = [vp, vp, ip, ip, f64, u64, u64, vp, ctypes.POINTER(LfgWdModel), vp, vp, vp, vp,
+                                       vp]
         if hasattr(L, "lfg_set_layout"):  # (older experiment builds lack it)
             L.lfg_set_layout.restype = ip
             L.lfg_set_layout.argtypes = [ip]
