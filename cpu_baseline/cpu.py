@@ -24,7 +24,8 @@ def build(out=None, march="x86-64-v3", extra=()):
     cmd = ["g++", "-O3", "-march=%s" % march, "-fopenmp", "-std=c++17", "-fPIC", "-shared"] + list(extra) + [
            "-I", HERE, "-I", os.path.join(HERE, "shim"), "-I", os.path.join(ROOT, "lfit_python_amd", "csrc"),
            "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp"),
-           os.path.join(HERE, "lfg_cpu_physpar.cpp"), os.path.join(HERE, "lfg_cpu_wd.cpp")]
+           os.path.join(HERE, "lfg_cpu_physpar.cpp"), os.path.join(HERE, "lfg_cpu_wd.cpp"),
+           os.path.join(HERE, "lfg_cpu_chain.cpp")]
     subprocess.run(cmd, check=True)
     return out
 
@@ -179,6 +180,53 @@ class CpuPort:
         if rc != 0:
             raise ValueError("lfg_cpu_wd_lnprob: code %d" % rc)
         return lnp, ll, np.ascontiguousarray(mags.T), st
+
+    def chain_stats(self, buf, steps, W, C, step_ld, walker_ld, offset=0, window=None, fracs=(), rhat=False):
+        """lfg_cpu_chain_stats on the view (include/lfg_chain.h) of the flat
+        float64 array `buf` that starts at element `offset`: a dict of n,
+        n_bad, mean, m2, min, max, ostat [C, nq, 2], quant [C, nq] and rhat."""
+        buf = np.ascontiguousarray(buf, dtype=np.float64).reshape(-1)
+        steps, W, C = int(steps), int(W), int(C)
+        if steps > 0 and W > 0:
+            assert offset + (steps - 1) * step_ld + (W - 1) * walker_ld + C <= buf.size
+        fr = np.ascontiguousarray(fracs, dtype=np.float64).reshape(-1)
+        nq = fr.size
+        win = None if window is None else np.ascontiguousarray(window, dtype=np.float64).reshape(C, 2)
+        out = {"n": np.empty(C, np.int64), "n_bad": np.empty(C, np.int64)}
+        for k in ("mean", "m2", "min", "max"):
+            out[k] = np.empty(C)
+        out["ostat"], out["quant"] = np.empty((C, nq, 2)), np.empty((C, nq))
+        out["rhat"] = np.empty(C) if rhat else None
+        f = self.lib.lfg_cpu_chain_stats
+        f.restype = ctypes.c_int
+        vp, i64 = ctypes.c_void_p, ctypes.c_longlong
+        f.argtypes = [vp, i64, i64, ctypes.c_int, i64, i64, vp, vp, ctypes.c_int] + [vp] * 9
+
+        def P(a):
+            return None if a is None else ctypes.c_void_p(a.ctypes.data)
+        rc = f(ctypes.c_void_p(buf.ctypes.data + 8 * int(offset)), steps, W, C, int(step_ld), int(walker_ld), P(win),
+               P(fr) if nq else None, nq, P(out["n"]), P(out["n_bad"]), P(out["mean"]), P(out["m2"]), P(out["min"]),
+               P(out["max"]), P(out["ostat"]), P(out["quant"]), P(out["rhat"]))
+        if rc != 0:
+            raise ValueError("lfg_cpu_chain_stats: code %d" % rc)
+        return out
+
+    def chain_clip(self, n, m2, med, sigma, window=None):
+        """lfg_cpu_chain_clip: the next window [C, 2]"""
+        n = np.ascontiguousarray(n, dtype=np.int64)
+        m2, med = (np.ascontiguousarray(a, dtype=np.float64) for a in (m2, med))
+        C = n.size
+        win = None if window is None else np.ascontiguousarray(window, dtype=np.float64).reshape(C, 2)
+        out = np.empty((C, 2))
+        f = self.lib.lfg_cpu_chain_clip
+        f.restype = ctypes.c_int
+        vp = ctypes.c_void_p
+        f.argtypes = [vp, vp, vp, ctypes.c_longlong, ctypes.c_double, vp, vp, ctypes.c_int]
+        rc = f(n.ctypes.data, m2.ctypes.data, med.ctypes.data, 1, float(sigma),
+               None if win is None else win.ctypes.data, out.ctypes.data, C)
+        if rc != 0:
+            raise ValueError("lfg_cpu_chain_clip: code %d" % rc)
+        return out
 
     def lnprob(self, walkers, tree, nthreads=0):
         """lfg_cpu_lnprob through a struct lfg_tree of host arrays"""

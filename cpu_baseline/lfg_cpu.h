@@ -13,6 +13,7 @@
 #include "lfg.h"
 #include "lfg_physpar.h"
 #include "lfg_wd.h"
+#include "lfg_chain.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -53,6 +54,18 @@ int lfg_cpu_physpar(const double* q, const double* dphi, const double* rwd,
 int lfg_cpu_wd_lnprob(const double* theta, size_t ld, int n,
                       const lfg_wd_model* model, double* lnp, double* lnlike,
                       double* mags, int* status, int nthreads);
+
+/* lfg_chain_stats' and lfg_chain_clip's twins (include/lfg_chain.h;
+ * MODEL_SPEC 14): the same arguments on host pointers, no scratch */
+int lfg_cpu_chain_stats(const double* base, long long steps, long long W, int C,
+                        long long step_ld, long long walker_ld,
+                        const double* window, const double* fracs, int nq,
+                        long long* n, long long* n_bad, double* mean, double* m2,
+                        double* vmin, double* vmax, double* ostat, double* quant,
+                        double* rhat);
+int lfg_cpu_chain_clip(const long long* n, const double* m2, const double* med,
+                       long long med_ld, double sigma, const double* win_in,
+                       double* win_out, int C);
 
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */

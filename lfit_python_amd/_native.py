@@ -28,7 +28,8 @@ SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "
            os.path.join(_HERE, "csrc", "lfg_pt.hip"),  # lfg_pt.hip: the parallel-tempering kernels, a unit of their own
            os.path.join(_HERE, "csrc", "lfg_gp_predict.hip"),  # the GP smoother and conditional sampler
            os.path.join(_HERE, "csrc", "lfg_physpar.hip"),  # physical parameters from chain rows (lfg_physpar.h)
-           os.path.join(_HERE, "csrc", "lfg_wd.hip")]  # the white-dwarf atmosphere fit (lfg_wd.h)
+           os.path.join(_HERE, "csrc", "lfg_wd.hip"),  # the white-dwarf atmosphere fit (lfg_wd.h)
+           os.path.join(_HERE, "csrc", "lfg_chain.hip")]  # a chain's summary (lfg_chain.h)
 # k_pair's fold and LONG instantiations: lfg.hip again, compiled on its own
 # without machine LICM (the reason: lfg.hip, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -37,7 +38,8 @@ SPLIT_FLAGS = ["-mllvm", "-disable-machine-licm"]
 HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
                  if f.endswith((".hpp", ".h"))) + [os.path.join(REPO, "include", "lfg.h"),
                                                    os.path.join(REPO, "include", "lfg_physpar.h"),
-                                                   os.path.join(REPO, "include", "lfg_wd.h")]
+                                                   os.path.join(REPO, "include", "lfg_wd.h"),
+                                                   os.path.join(REPO, "include", "lfg_chain.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 
@@ -129,6 +131,12 @@ class LfgWdModel(ctypes.Structure):
         ("prior_p2", ctypes.c_double * WD_NPAR), ("prior_c0", ctypes.c_double * WD_NPAR),
         ("prior_c1", ctypes.c_double * WD_NPAR),
     ]
+
+
+# include/lfg_chain.h: the chain's summary, a set of its own too
+EXPORTS_CHAIN = ("lfg_chain_workspace_size", "lfg_chain_tile_rows", "lfg_chain_hist_tile", "lfg_chain_stats",
+                 "lfg_chain_clip")
+CHAIN_MAX_C, CHAIN_MAX_NQ = 4096, 8  # LFG_CHAIN_* (include/lfg_chain.h)
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -325,6 +333,18 @@ def lib():
         L.lfg_wd_step_half.restype = ip
         L.lfg_wd_step_half.argtypes = [vp, vp, ip, ip, f64, u64, u64, vp, ctypes.POINTER(LfgWdModel), vp, vp, vp, vp,
                                        vp]
+        i64 = ctypes.c_longlong
+        L.lfg_chain_workspace_size.restype = sz
+        L.lfg_chain_workspace_size.argtypes = [i64, i64, ip, ip]
+        L.lfg_chain_tile_rows.restype = ip
+        L.lfg_chain_tile_rows.argtypes = []
+        L.lfg_chain_hist_tile.restype = ip
+        L.lfg_chain_hist_tile.argtypes = [ip]
+        L.lfg_chain_stats.restype = ip
+        L.lfg_chain_stats.argtypes = [vp, i64, i64, ip, i64, i64, vp, ctypes.POINTER(f64), ip, vp, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp, sz, vp]
+        L.lfg_chain_clip.restype = ip
+        L.lfg_chain_clip.argtypes = [vp, vp, vp, i64, f64, vp, vp, ip, vp]
         if hasattr(L, "lfg_set_layout"):  # (older experiment builds lack it)
             L.lfg_set_layout.restype = ip
             L.lfg_set_layout.argtypes = [ip]

@@ -1,0 +1,32 @@
+"""The summary of a finished chain file: modparams.csv and the before/after
+report of the reference's fit_summary (chainstats.fit_summary).
+
+    python -m lfit_python_amd.fit_summary CHAIN INPUT [--nskip N] [--thin K] [--dir D]
+"""
+import argparse
+import sys
+
+from . import chainstats, sampler
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Summarise a chain file: modparams.csv and the model's report.")
+    ap.add_argument("chain", help="a chain file as the MCMC driver writes it (chain_prod.txt)")
+    ap.add_argument("input", help="the MCMC parameters' input file of that run")
+    ap.add_argument("--nskip", type=int, default=0)
+    ap.add_argument("--thin", type=int, default=1)
+    ap.add_argument("--dir", default=".", help="where modparams.csv goes")
+    args = ap.parse_args(argv)
+    with open(args.chain) as fh:
+        names = fh.readline().split()[1:-1]   # 'walker_no <names> ln_prob'
+    chain = sampler.read_chain(args.chain)    # [W][steps][npars + 1]
+    out = chainstats.fit_summary(chain, names, input_file=args.input, nskip=args.nskip, thin=args.thin,
+                                 out_dir=args.dir, walker_major=True)
+    print("Result of the chain:")
+    print(out["result"].to_string())
+    print("Wrote {}".format(out["modparams"]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -11,6 +11,7 @@ device-resident EnsembleSampler: same names, arguments and file formats.
   flatchain(chain, npars=None, nskip=0, thin=1)                 mcmc_utils.py:242-249
   readchain(file) / readchain_dask(file)                        mcmc_utils.py:252-300
   readflatchain(file)                                           mcmc_utils.py:303-306
+  GR_diagnostic(sampler_chain)   (chainstats.gr_diagnostic)     mcmc_utils.py:317-351
   posterior_predictive(ev, samples, chunk=)   the numbers behind
                                               plot_lc_model.plot_GP_eclipse
 
@@ -23,6 +24,8 @@ and writes it in bulk chunks instead of re-opening the file for every row
 import numpy as np
 
 from . import sampler as _sampler
+from .chainstats import gr_diagnostic
+from .chainstats import gr_diagnostic as GR_diagnostic  # the reference's name
 
 
 def initialise_walkers(p, scatter, nwalkers, ln_prior, model=None, seed=0):

@@ -18,7 +18,10 @@ With usePT = 1 the run is parallel-tempered over ntemps temperature levels
 walker ball per level, burn-in, with double_burnin a re-scatter of every
 level about the best cold walker, reset, and the cold level's chain written
 to chain_prod.txt with its log posterior as ln_prob.  One process only.
-The plots / e-mailed summary are out of scope.
+With --summary (run(..., summary=True)) rank 0 then summarises the production
+chain where it lies on the device (chainstats.fit_summary) and writes
+modparams.csv next to the chain file.  The plots and the e-mail are out of
+scope.
 """
 import argparse
 import os
@@ -72,7 +75,8 @@ def degrees_of_freedom(model):
     return dof - len(model.dynasty_par_names) - 1
 
 
-def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt", chunk=None, log=print):
+def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt", chunk=None, log=print,
+        summary=False):
     import torch
     dist = torch.distributed
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -113,6 +117,9 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
 
     tree = batch.compile_tree(model)
     if rc["usePT"]:
+        if summary:  # (the cold chain is written in chunks and not kept: summarise the file)
+            raise NotImplementedError("summary=True with usePT = 1: run python -m lfit_python_amd.fit_summary "
+                                      "on the chain file")
         return _run_pt(rc, tree, names, pars, s1, s2, dev, seed, chain_file, chunk, say)
     ev = batch.LnProbEvaluator(tree, device=dev, max_walkers=nwalkers)
     prior_fn = lambda p: ev.ln_prior(torch.as_tensor(p, device=dev)).cpu().numpy()
@@ -143,10 +150,21 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
         first = False
         done += k
     acc = float(np.mean(S.acceptance_fraction))
+    summ = _summarise(S.chain_dev, S.lnprob_dev, names, input_file, chain_file, say) if summary and rank == 0 else None
     S.close()  # the direct RCCL communicator, before the process group goes
     say("Mean acceptance fraction: {:.3f}".format(acc))
-    return {"status": "ok", "chain_file": chain_file, "acceptance": acc, "nwalkers": nwalkers, "npars": npars,
-            "nprod": nprod}
+    out = {"status": "ok", "chain_file": chain_file, "acceptance": acc, "nwalkers": nwalkers, "npars": npars,
+           "nprod": nprod}
+    if summary:
+        out["summary"] = summ
+    return out
+
+
+def _summarise(chain, lnprob, names, input_file, chain_file, say):
+    """the production chain's summary, from the device tensors"""
+    from . import chainstats
+    return chainstats.fit_summary(chain, names, input_file=input_file,
+                                  out_dir=os.path.dirname(os.path.abspath(chain_file)), lnprob=lnprob, log=say)
 
 
 def _run_pt(rc, tree, names, pars, s1, s2, dev, seed, chain_file, chunk, say):
@@ -188,13 +206,16 @@ def main(argv=None):
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--chain", default="chain_prod.txt")
+    ap.add_argument("--summary", action="store_true",
+                    help="summarise the production chain on the device: modparams.csv next to the chain file")
     args = ap.parse_args(argv)
     import torch
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local))
-    out = run(args.input, quiet=args.quiet, debug=args.debug, seed=args.seed, chain_file=args.chain)
+    out = run(args.input, quiet=args.quiet, debug=args.debug, seed=args.seed, chain_file=args.chain,
+              summary=args.summary)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     # the reference leaves through a bare exit() (status 0) for a report-only
