@@ -1,6 +1,7 @@
 // lfg_philox.hpp -- the samplers' counter-based random numbers, shared by
-// lfg.hip (stretch move) and lfg_pt.hip (parallel tempering).  Included
-// inside each unit's anonymous namespace, after <hip/hip_runtime.h>.
+// lfg.hip (stretch move: ahead of k_setup, whose speculative lanes draw
+// too) and lfg_pt.hip (parallel tempering).  Included inside each unit's
+// anonymous namespace, after <hip/hip_runtime.h>.
 // The counter layout of every draw is documented in include/lfg.h.
 #ifndef LFG_PHILOX_HPP
 #define LFG_PHILOX_HPP

@@ -10,7 +10,7 @@
 // LDS per launch would cost more loads than the launch makes.
 //
 // k_wd_step_half: one lane per walker of the half: k_propose's draws and
-// arithmetic (lfg.hip), wd_row, k_accept's draw and rule.  A lane reads rows
+// arithmetic (lfg_k_stretch.hpp), wd_row, k_accept's draw and rule.  A lane reads rows
 // of the other half only, and writes only its own walker's row, so no lane
 // waits for another.
 #include <hip/hip_runtime.h>

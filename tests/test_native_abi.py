@@ -207,6 +207,26 @@ def test_source_hash_covers_every_included_header(tmp_path, monkeypatch):
     assert _native.source_hash() == want
 
 
+def test_split_unit_compiles_k_pairs_three_instantiations_only(tmp_path):
+    """lfg_pair_split.hip compiles lfg.hip a second time (LFG_NOLICM_TU) for
+    k_pair<false, FOLD, LONG>, FOLD or LONG set, and for nothing else: a
+    kernel added to lfg.hip or a header of its without a guard would come out
+    of both units, twice in the library.  And no other file includes lfg.hip."""
+    out = tmp_path / "split.s"
+    subprocess.run(["hipcc"] + [f for f in _native.FLAGS if f != "-shared"] + _native.SPLIT_FLAGS +
+                   ["-I", _native.INCLUDE, "--cuda-device-only", "-S", "-o", str(out), _native.SPLIT_SOURCE], check=True)
+    kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", out.read_text(), flags=re.M)
+    assert sorted(kernels) == ["_ZN12_GLOBAL__N_16k_pairILb0ELb0ELb1EEEvNS_8PairArgsE",   # <false, false, true>
+                               "_ZN12_GLOBAL__N_16k_pairILb0ELb1ELb0EEEvNS_8PairArgsE",   # <false, true, false>
+                               "_ZN12_GLOBAL__N_16k_pairILb0ELb1ELb1EEEvNS_8PairArgsE"]   # <false, true, true>
+    csrc = os.path.dirname(_native.SPLIT_SOURCE)
+    sources = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".hpp", ".h"))]
+    assert os.path.basename(_native.SPLIT_SOURCE) in sources and len(sources) >= 10
+    for name in sources:
+        if name != os.path.basename(_native.SPLIT_SOURCE):
+            assert '#include "lfg.hip"' not in open(os.path.join(csrc, name)).read(), name
+
+
 def test_foreign_library_refused(tmp_path):
     """LFG_LIB without LFG_DIAGNOSTIC=1 is refused at import; with it, a
     library carrying another source hash fails verify() (what smoke() and the

@@ -28,7 +28,7 @@ F_ACC_ECL = 3    # overlap |[a,b] n window| (1 sub) + weighted accumulate (1 fma
 F_ACC_DON = 6    # projection dA n.e (1 mul + 2 fma) + max(0, .) accumulate (1 add)
 F_POINT = 40     # per point per sub-phase: phase wrap, sincospi, beaming, donor normalisation, chi^2 share
 N_ECL, N_DON = 1500, 400
-# k_gp_like (lfg.hip), parallel in time: per point, the element pass of its
+# k_gp_like (lfg_k_gp.hpp), parallel in time: per point, the element pass of its
 # segment on a lane quad -- per lane: prediction of its D row, A column and
 # c_r 31, gain / innovation / J, eta, c, A, D updates 52, the point's
 # transition factors 3 -> 4 x 86; per segment (8 per pair) the 4x4 combine
