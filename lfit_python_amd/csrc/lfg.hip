@@ -1504,8 +1504,11 @@ __device__ __forceinline__ double2 direct_wd_disc(const double2* __restrict__ AB
 {
     double ewd = 0.0, ed = 0.0;
     const double lo = phc - wk, hi = phc + wk;
+    // MODEL_SPEC 3: a width below the spacing of the doubles at phc (hi == lo) leaves no window either and is
+    // the point evaluation, as a zero one is; "nothing overlaps" would be flux 1 inside an eclipse
+    const bool window = hi > lo;
     auto cover = [&](double2 ab) {
-        return (wk > 0.0) ? fmax(fmin(ab.y, hi) - fmax(ab.x, lo), 0.0) : ((phc > ab.x && phc < ab.y) ? 1.0 : 0.0);
+        return window ? fmax(fmin(ab.y, hi) - fmax(ab.x, lo), 0.0) : ((phc > ab.x && phc < ab.y) ? 1.0 : 0.0);
     };
     for (int ring = 0; ring < NWD_RINGS + NDISC_R; ++ring) {  // each unique item and its mirror
         const int u0 = ring < NWD_RINGS ? 2 * ring * ring : U_WD + (ring - NWD_RINGS) * (NDISC_AZ / 2);
@@ -1517,7 +1520,7 @@ __device__ __forceinline__ double2 direct_wd_disc(const double2* __restrict__ AB
         }
         if (ring < NWD_RINGS) ewd = fma(swr[ring], acc, ewd); else ed = fma(swr[ring], acc, ed);
     }
-    const double nrm = (wk > 0.0) ? 1.0 / (2.0 * wk) : 1.0;
+    const double nrm = window ? 1.0 / (2.0 * wk) : 1.0;
     return make_double2(ewd * nrm * (1.0 / twd), ed * nrm * (1.0 / td));
 }
 
@@ -1528,10 +1531,10 @@ __device__ __forceinline__ double direct_spot(const double2* ABs, const double* 
     const double l2 = ph - h, h2 = ph + h;
     for (int k = 0; k < NBS; ++k) {
         const double2 ab = ABs[k];
-        eb = fma(sbw[k], (h > 0.0) ? fmax(fmin(ab.y, h2) - fmax(ab.x, l2), 0.0)
+        eb = fma(sbw[k], (h2 > l2) ? fmax(fmin(ab.y, h2) - fmax(ab.x, l2), 0.0)  // MODEL_SPEC 3, as direct_wd_disc
                                    : ((ph > ab.x && ph < ab.y) ? 1.0 : 0.0), eb);
     }
-    return eb * ((h > 0.0) ? 1.0 / (2.0 * h) : 1.0) * itb;
+    return eb * ((h2 > l2) ? 1.0 / (2.0 * h) : 1.0) * itb;
 }
 
 // direct donor sum for one line of sight e = (e0, e1, c)
@@ -2885,8 +2888,11 @@ __device__ __forceinline__ double2 pair_direct_wd_disc(const double2* __restrict
 {
     double ewd = 0.0, ed = 0.0;
     const double lo = phc - wk, hi = phc + wk;
+    // MODEL_SPEC 3: a width below the spacing of the doubles at phc (hi == lo) leaves no window either and is
+    // the point evaluation, as a zero one is; "nothing overlaps" would be flux 1 inside an eclipse
+    const bool window = hi > lo;
     auto cover = [&](double2 ab) {
-        return (wk > 0.0) ? fmax(fmin(ab.y, hi) - fmax(ab.x, lo), 0.0) : ((phc > ab.x && phc < ab.y) ? 1.0 : 0.0);
+        return window ? fmax(fmin(ab.y, hi) - fmax(ab.x, lo), 0.0) : ((phc > ab.x && phc < ab.y) ? 1.0 : 0.0);
     };
     for (int ring = 0; ring < NWD_RINGS + NDISC_R; ++ring) {  // each unique item and its mirror
         const int u0 = ring < NWD_RINGS ? 2 * ring * ring : U_WD + (ring - NWD_RINGS) * (NDISC_AZ / 2);
@@ -2899,7 +2905,7 @@ __device__ __forceinline__ double2 pair_direct_wd_disc(const double2* __restrict
         const double wr = ring < NWD_RINGS ? wd_ring_weight(ring, ul) : swt[ring - NWD_RINGS];
         if (ring < NWD_RINGS) ewd = fma(wr, acc, ewd); else ed = fma(wr, acc, ed);
     }
-    const double nrm = (wk > 0.0) ? 1.0 / (2.0 * wk) : 1.0;
+    const double nrm = window ? 1.0 / (2.0 * wk) : 1.0;
     return make_double2(ewd * nrm * (1.0 / twd), ed * nrm * (1.0 / td));
 }
 
@@ -3076,8 +3082,9 @@ __device__ __forceinline__ double long_point(const LongTabs& W, const LongU& K, 
 __device__ __forceinline__ double2 long_wd_disc(const LongTabs& W, const LongU& K, double phc, double wk,
                                                int* ctr = nullptr)
 {
-    if (wk > 0.0) {
-        const double lo = phc - wk, hi = phc + wk, iw = FX_INV / (hi - lo);  // -lo - -hi = hi - lo exactly
+    const double lo = phc - wk, hi = phc + wk;
+    if (hi > lo) {  // not wk > 0: a width below the spacing of the doubles at phc is a point (MODEL_SPEC 3)
+        const double iw = FX_INV / (hi - lo);  // -lo - -hi = hi - lo exactly
         return make_double2(long_window(W, K, 0, lo, hi, iw, ctr) + long_window(W, K, 0, -hi, -lo, iw, ctr),
                             long_window(W, K, 1, lo, hi, iw, ctr) + long_window(W, K, 1, -hi, -lo, iw, ctr));
     }

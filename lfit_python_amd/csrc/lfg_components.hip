@@ -198,7 +198,9 @@ __global__ __launch_bounds__(64) void k_comp_elements(int kind, int W, int n1, i
         const int ir = k / n2, j = k - ir * n2;
         const double rin = G[C_P0], dr = (G[C_P1] - rin) / n1, ex = G[C_P2];
         const double r0 = rin + ir * dr, r1 = rin + (ir + 1) * dr, rc = 0.5 * (r0 + r1);
-        const double I = (fabs(ex) < 1e-10) ? log(r1 / r0) : (pow(r1, ex) - pow(r0, ex)) / ex;
+        // r0^ex expm1(ex ln(r1 / r0)) / ex, not the difference of two powers (MODEL_SPEC 5.2)
+        const double lr = log(r1 / r0);
+        const double I = (fabs(ex) < 1e-10) ? lr : pow(r0, ex) * expm1(ex * lr) / ex;
         wgt = (TWO_PI / n2) * I;
         double sa, ca;
         sincos(TWO_PI * (j + 0.5) / n2, &sa, &ca);
@@ -263,6 +265,9 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_comp_flux(int kind, int nel, con
         sincospi(2.0 * ph, &sn, &cs);
         const double e0 = s * cs, e1 = -s * sn;
         const double lo = ph - h, hi = ph + h;
+        // MODEL_SPEC 3: a width below the spacing of the doubles at ph leaves no window and is a point
+        // evaluation, its limit, as a zero or negative one is; a NaN width gives a NaN flux
+        const bool window = h > 0.0 && hi > lo;
         double acc = 0.0;
         for (int k0 = 0; k0 < nel; k0 += COMP_TILE) {
             const int m = min(COMP_TILE, nel - k0);
@@ -272,7 +277,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_comp_flux(int kind, int nel, con
             if (kind == 3) {
                 for (int j = 0; j < m; ++j)
                     acc += fmax(se[3 * j] * e0 + se[3 * j + 1] * e1 + se[3 * j + 2] * c, 0.0);
-            } else if (h > 0.0) {  // exact overlap of the window with the eclipse interval
+            } else if (window) {  // exact overlap of the window with the eclipse interval
                 for (int j = 0; j < m; ++j)
                     acc += se[3 * j + 2] * fmax(fmin(se[3 * j + 1], hi) - fmax(se[3 * j], lo), 0.0);
             } else {
@@ -285,7 +290,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_comp_flux(int kind, int nel, con
         if (kind == 3) {
             f = acc / tot;
         } else {
-            const double ecl = (h > 0.0) ? acc / (2.0 * h) : acc;  // eclipsed weight
+            const double ecl = window ? acc / (2.0 * h) : acc;  // eclipsed weight
             f = (tot - ecl) / tot;
             if (kind == 2) {
                 const double bden = G[C_BDEN], fis = G[C_FIS];
@@ -295,7 +300,7 @@ __global__ __launch_bounds__(COMP_BLOCK) void k_comp_flux(int kind, int nel, con
                 f *= beam;
             }
         }
-        o[p] = f;
+        o[p] = isnan(h) ? NAN : f;
     }
 }
 
