@@ -260,6 +260,20 @@ int lfg_lnprob_timed(const double* walkers, int W, const lfg_tree* tree,
  *   pos [dev] W x ndim (updated in place by accept), lnp [dev] W
  *   q   [dev] W/2 x ndim proposals, zfac [dev] W/2 = (ndim-1) ln z
  *   lnp_new [dev] W/2 ln_prob of q;  naccept [dev] W acceptance counters
+ * The draw of walker i of the half, from r = Philox(counter (i, step lo,
+ * step hi, 2 half), key seed):
+ *   u = u53(r.x, r.y),  z = zr zr / a  with  zr = fma(a - 1, u, 1),
+ *   partner j = __umulhi(r.z, W/2),  row q = fma(s - c_j, z, c_j).
+ * (a - 1) u + 1 is ONE fma (one rounding): that reading is the contract.
+ * For an a whose a - 1 is not a power of two it differs in the last bit, on
+ * a few per cent of the draws, from the product and the sum rounded in turn.
+ * Every entry point below that forms or re-forms a proposal (the fused and
+ * sharded half-steps, their speculative and deferred variants, accept_regen,
+ * apply_verdicts, lfg_pt_propose, the half-step of lfg_wd.h) states this draw again,
+ * and wherever this header says "bit-identical", "same chain" or "same
+ * draws" the claim holds for every a > 1, every ensemble size W >= 4, every
+ * shard (lo, n) and every 64-bit seed and step, not only a = 2
+ * (tests/test_gpu_sampler_double.py holds each of them to one host double).
  */
 int lfg_stretch_propose(const double* pos, int W, int ndim, int half,
                         double a, unsigned long long seed,

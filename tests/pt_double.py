@@ -3,30 +3,22 @@ lfg_pt_accept / lfg_pt_swap): a NumPy statement of the moves with the
 kernels' exact Philox counter layout (include/lfg.h), built on
 stretch_double's Philox.  Used to check the HIP kernels draw for draw and to
 run sampler.PTSampler on CPU (TorchCpuPTOps)."""
-from fractions import Fraction
-
 import numpy as np
 
-from tests.stretch_double import MASK, draw, philox, u53
-
-
-def _fma1(a, b, c):
-    return float(Fraction(a) * Fraction(b) + Fraction(c))   # one rounding, as the device's fma
-
-
-_fma = np.frompyfunc(_fma1, 3, 1)
+from tests.stretch_double import MASK, Z_CONTRACTED, _fma, draw, philox, u53, z_of
 
 
 def propose(pos, half, a, seed, step, exact=False):
     """pos [T, W, ndim] -> q [T * W/2, ndim], zfac [T * W/2]; proposal
     g = t * W/2 + i is walker i of half `half` of level t.  exact: the
-    kernel's fma(s - c, z, c) in exact rational arithmetic (bit-identical
-    rows; slow), else c + (s - c) z with two roundings."""
+    kernel's fma(s - c, z, c) and fma(a - 1, u, 1) in exact rational
+    arithmetic (bit-identical rows; slow), else c + (s - c) z and
+    (a - 1) u + 1 with two roundings each."""
     T, W, ndim = pos.shape
     ns = W // 2
     r = draw(seed, step, half, 0, T * ns)
     u = u53(r[0], r[1])
-    z = ((a - 1.0) * u + 1.0) ** 2 / a
+    z = z_of(u, a, Z_CONTRACTED) if exact else ((a - 1.0) * u + 1.0) ** 2 / a
     j = ((r[2] * np.uint64(ns)) >> np.uint64(32)).astype(np.int64)
     t = np.repeat(np.arange(T), ns)
     s = pos[:, half * ns:(half + 1) * ns].reshape(T * ns, ndim)

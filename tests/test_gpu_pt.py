@@ -58,15 +58,14 @@ def _start(T, W, ndim, seed):
     return p0
 
 
-@pytest.mark.parametrize("T,W,ndim", [(1, 4, 3), (2, 36, 87), (5, 64, 18), (3, 2052, 5)])
-def test_kernels_match_the_double_draw_for_draw(T, W, ndim):
+def _draw_for_draw(T, W, ndim, a, seed):
     """Three full iterations, every stage compared: proposals to 1e-14
     relative; permutations, acceptances, swap decisions, counters and the
     state pos / lnl / lnpr exactly.  Among the proposals are ln_prob = -inf
     and NaN ones (none may move its walker)."""
     import torch
     from lfit_python_amd import sampler
-    seed, a, ns = 1234 + W, 2.0, W // 2
+    ns = W // 2
     dev = torch.device("cuda")
     betas = sampler.default_betas(ndim, T)
     ops, ev_d, ev_h = sampler.HipPTOps(dev), ToyTree(dev), ToyTree("cpu")
@@ -129,6 +128,19 @@ def test_kernels_match_the_double_draw_for_draw(T, W, ndim):
     assert 0 < moved < 6 * T * ns
     if T > 1:
         assert np.all(nswap[1:, 0] == 3 * W) and np.all((0 < nswap[1:, 1]) & (nswap[1:, 1] < 3 * W))
+
+
+@pytest.mark.parametrize("T,W,ndim", [(1, 4, 3), (2, 36, 87), (5, 64, 18), (3, 2052, 5)])
+def test_kernels_match_the_double_draw_for_draw(T, W, ndim):
+    _draw_for_draw(T, W, ndim, 2.0, 1234 + W)
+
+
+@pytest.mark.parametrize("T,W,ndim", [(1, 4, 3), (2, 36, 87)])
+def test_kernels_match_the_double_off_a2(T, W, ndim):
+    """the same comparison at a = 2.5 and a seed past 2^32: (a - 1) u is no
+    longer exact, so k_pt_propose's z must be the double's fma(a - 1, u, 1)
+    reading (stretch_double.z_of) for the accepted rows to equal the host's"""
+    _draw_for_draw(T, W, ndim, 2.5, 2**40 + 7 + W)
 
 
 def test_swap_at_the_largest_ensemble():

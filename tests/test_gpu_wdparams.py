@@ -209,12 +209,11 @@ def _start(ev, W, seed):
     return sampler.initialise_walkers(np.array([13000.0, 8.2, 2.4, 0.006]), 0.05, W, f, seed=seed)
 
 
-@pytest.mark.parametrize("W", (8, 130, 514))
-def test_fused_half_step_matches_three_launches(ev, W):
+def _fused_matches_three_launches(ev, W, a, seed):
     import torch
     from lfit_python_amd import sampler
     p0 = _start(ev, W, seed=W)
-    fused, three, graph = (sampler.EnsembleSampler(W, 4, ev, seed=77) for _ in range(3))
+    fused, three, graph = (sampler.EnsembleSampler(W, 4, ev, a=a, seed=seed) for _ in range(3))
     assert fused.fuse and three.fuse
     three.fuse = graph.fuse = False
     graph.use_graph = True
@@ -229,6 +228,52 @@ def test_fused_half_step_matches_three_launches(ev, W):
         assert _same((fused.q, fused.zfac, fused.lnp_new), (three.q, three.zfac, three.lnp_new)), step
     assert graph._graph is not None                      # the replay path ran
     assert int(three.naccept.sum()) > 0 and int((three.naccept < 5).sum()) > 0   # both verdicts occurred
+
+
+@pytest.mark.parametrize("W", (8, 130, 514))
+def test_fused_half_step_matches_three_launches(ev, W):
+    _fused_matches_three_launches(ev, W, 2.0, 77)
+
+
+def test_fused_half_step_matches_three_launches_off_a2(ev):
+    """a = 2.5, a seed past 2^32: (a - 1) u is no longer exact, so the fused
+    kernel's fma(a - 1, u, 1) must be what k_propose's unit forms"""
+    _fused_matches_three_launches(ev, 130, 2.5, 2**40 + 77)
+
+
+def test_fused_half_step_matches_the_exact_double_off_a2(ev):
+    """lfg_wd_step_half at a = 2.5, seed and step past 2^32, against the
+    stretch move's host double in the device's arithmetic: rows bit-identical,
+    zfac to 1e-15, and with the device's own ln_prob of the proposals the
+    host's verdicts, ensemble and counters exactly"""
+    import torch
+    from lfit_python_amd import _native
+    from tests import stretch_double as sd
+    W, a, seed, step = 130, 2.5, 2**40 + 7, 2**32 + 3
+    ns = W // 2
+    p0 = _start(ev, W, seed=3)
+    P0 = torch.as_tensor(p0, device=ev.device)
+    lnp0 = ev(P0)
+    f64 = dict(dtype=torch.float64, device=ev.device)
+    taken = 0
+    for half in (0, 1):
+        pos, lnp = P0.clone(), lnp0.clone()
+        q, zf, new = torch.empty((ns, 4), **f64), torch.empty(ns, **f64), torch.empty(ns, **f64)
+        nacc = torch.zeros(W, dtype=torch.int32, device=ev.device)
+        rc = _native.lib().lfg_wd_step_half(ag.ptr(pos), ag.ptr(lnp), W, half, a, seed, step, None,
+                                            ctypes.byref(ev.M), ag.ptr(q), ag.ptr(zf), ag.ptr(new), ag.ptr(nacc),
+                                            _native.stream_ptr(ev.device))
+        assert rc == 0
+        qh, zh = sd.propose(p0, half, a, seed, step, exact=True)
+        np.testing.assert_array_equal(q.cpu().numpy(), qh)
+        np.testing.assert_allclose(zf.cpu().numpy(), zh, rtol=1e-15, atol=1e-15)
+        ph, lh, nh = p0.copy(), lnp0.cpu().numpy().copy(), np.zeros(W, np.int64)
+        acc = sd.accept(ph, lh, half, qh, zh, new.cpu().numpy(), seed, step, nh)
+        np.testing.assert_array_equal(pos.cpu().numpy(), ph)
+        np.testing.assert_array_equal(lnp.cpu().numpy(), lh)
+        np.testing.assert_array_equal(nacc.cpu().numpy(), nh)
+        taken += int(acc.sum())
+    assert 0 < taken < W
 
 
 def test_fused_half_step_reads_a_device_step_counter(ev):
