@@ -2,7 +2,7 @@
 // combines k_combine_walkers and k_combine.  Needs before it: lfg_device.hpp
 // (findphi_fast, element_interval, eggleton), lfg_philox.hpp (draw, u53),
 // and lfg.hip's sections k_elements (prior_rejects), k_lnlike (LikeArgs,
-// combine_walker, combine_after) and k_pair (DCP_LANES, DCP_NTHETA).
+// combine_walker, combine_after) and lfg_k_pair.hpp (DCP_LANES, DCP_NTHETA).
 // Included in lfg.hip's anonymous namespace, not in lfg_pair_split.hip's
 // unit (LFG_NOLICM_TU).
 #pragma once

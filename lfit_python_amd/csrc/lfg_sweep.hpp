@@ -1,7 +1,7 @@
 // lfg_sweep.hpp -- the tile sweep's arithmetic: the phase index over a tile's
 // sorted windows, an element's runs over them, and the entries the runs add to
 // a difference array (int64 fixed point, so that the sums are exact in any
-// order).  Shared by k_lnlike, k_pair's sinks (lfg.hip) and, through
+// order).  Shared by k_lnlike (lfg.hip), k_pair's sinks (lfg_k_pair.hpp) and, through
 // cpu_baseline/shim, host programs: the add itself goes through a functor
 // (an LDS atomic on the device) and the wave vote of apply_runs_merged through
 // another (the lane's own predicate on the host).

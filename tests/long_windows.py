@@ -1,7 +1,7 @@
 """k_pair LONG's exposure windows by class, and the quiet window's closed form
 in numpy (no GPU).
 
-sub_point_quiet (lfit_python_amd/csrc/lfg.hip) sums a window's S sub-bins in
+sub_point_quiet (lfit_python_amd/csrc/lfg_k_pair_long.hpp) sums a window's S sub-bins in
 closed form when nothing changes inside it, and hands every other window to
 the sub-bin loop.  classify() restates its conditions from the oracle's
 element tables (oracle.elements, oracle.findi), in the kernel's order of

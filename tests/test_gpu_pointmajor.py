@@ -2,7 +2,7 @@
 
 A tile goes point-major when any of its exposure windows is out of order
 (lo, hi or phase below its predecessor's) or has a negative or NaN width
-(lfg.hip k_pair prologue: the sortedness flags); the element phase then writes
+(lfg_k_pair.hpp: k_pair's prologue, the sortedness flags); the element phase then writes
 its tables into LDS and every point scans them (pair_direct_wd_disc,
 direct_spot, direct_donor).  The reference accepts such light curves:
 Lightcurve.from_calib keeps the file's order and sets w = mean(diff(x))/2,

@@ -5,6 +5,7 @@ import ctypes
 import os
 import re
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -211,11 +212,25 @@ def test_split_unit_compiles_k_pairs_three_instantiations_only(tmp_path):
     """lfg_pair_split.hip compiles lfg.hip a second time (LFG_NOLICM_TU) for
     k_pair<false, FOLD, LONG>, FOLD or LONG set, and for nothing else: a
     kernel added to lfg.hip or a header of its without a guard would come out
-    of both units, twice in the library.  And no other file includes lfg.hip."""
-    out = tmp_path / "split.s"
-    subprocess.run(["hipcc"] + [f for f in _native.FLAGS if f != "-shared"] + _native.SPLIT_FLAGS +
-                   ["-I", _native.INCLUDE, "--cuda-device-only", "-S", "-o", str(out), _native.SPLIT_SOURCE], check=True)
-    kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", out.read_text(), flags=re.M)
+    of both units, twice in the library.  So the two units' kernel sets are
+    disjoint and the main unit holds the kernels the split unit leaves out.
+    And no other file includes lfg.hip."""
+    def kernels_of(source, extra, name):
+        out = tmp_path / name
+        subprocess.run(["hipcc"] + [f for f in _native.FLAGS if f != "-shared"] + extra +
+                       ["-I", _native.INCLUDE, "--cuda-device-only", "-S", "-o", str(out), source], check=True)
+        return re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", out.read_text(), flags=re.M)
+
+    assert os.path.basename(_native.SOURCES[0]) == "lfg.hip"
+    with ThreadPoolExecutor(2) as pool:  # (the two compiles side by side: the wall time of the main unit's alone)
+        split_job = pool.submit(kernels_of, _native.SPLIT_SOURCE, _native.SPLIT_FLAGS, "split.s")
+        main_job = pool.submit(kernels_of, _native.SOURCES[0], [], "main.s")
+        kernels, main = split_job.result(), main_job.result()
+    assert len(main) == len(set(main)) and not set(main) & set(kernels), sorted(set(main) & set(kernels))
+    assert "_ZN12_GLOBAL__N_16k_pairILb0ELb0ELb0EEEvNS_8PairArgsE" in main   # <false, false, false>
+    for name in ("k_setup", "k_elements", "k_expand"):  # (mangled: length, name, E, then the argument types)
+        prefix = "_ZN12_GLOBAL__N_1%d%sE" % (len(name), name)
+        assert sum(1 for k in main if k.startswith(prefix)) == 1, (name, main)
     assert sorted(kernels) == ["_ZN12_GLOBAL__N_16k_pairILb0ELb0ELb1EEEvNS_8PairArgsE",   # <false, false, true>
                                "_ZN12_GLOBAL__N_16k_pairILb0ELb1ELb0EEEvNS_8PairArgsE",   # <false, true, false>
                                "_ZN12_GLOBAL__N_16k_pairILb0ELb1ELb1EEEvNS_8PairArgsE"]   # <false, true, true>

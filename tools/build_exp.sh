@@ -1,7 +1,8 @@
 #!/bin/bash
 # Experiment/diagnostic builds of liblfg_hip.so: build/exp/liblfg_<name>.so
 # with extra compile flags, loaded through LFG_LIB (lfit_python_amd/_native.py).
-# usage: tools/build_exp.sh <name> [-DFLAG ...]   (LFG_SRC=<file>: another lfg.hip, e.g. a commit's)
+# usage: tools/build_exp.sh <name> [-DFLAG ...]   (LFG_SRC=<file>: another lfg.hip; it includes
+#        the lfg_k_*.hpp headers by name, so it sits in lfit_python_amd/csrc/ next to them)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift

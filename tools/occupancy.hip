@@ -1,6 +1,7 @@
 // Diagnostic: resident blocks per CU of the lfg kernels (occupancy API) and
 // of probe kernels that isolate the LDS and VGPR limits.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include tools/occupancy.hip -o build/occupancy
+#define LFG_ONE_TU 1  // every kernel in this unit: there is no lfg_pair_split.hip to link
 #include "../lfit_python_amd/csrc/lfg.hip"
 #include <cstdio>
 
@@ -32,9 +33,10 @@ int main()
            p.sharedMemPerBlock, p.maxSharedMemoryPerMultiProcessor, p.regsPerBlock);
     report("k_setup", k_setup, SETUP_BLOCK);
     report("k_elements", k_elements, ELEM_BLOCK);
-    report("k_lnlike<0>", k_lnlike<0>, LIKE_THREADS);
-    report("k_lnlike<1>", k_lnlike<1>, LIKE_THREADS);
-    report("k_lnlike<2>", k_lnlike<2>, LIKE_THREADS);
+    report("k_lnlike<0, false>", k_lnlike<0, false>, LIKE_THREADS);
+    report("k_lnlike<1, false>", k_lnlike<1, false>, LIKE_THREADS);
+    report("k_lnlike<1, true>", k_lnlike<1, true>, LIKE_THREADS);
+    report("k_lnlike<2, false>", k_lnlike<2, false>, LIKE_THREADS);
     report("probe_lds<32768>", probe_lds<32768>, 512);
     report("probe_lds<65536>", probe_lds<65536>, 512);
     report("probe_lds<67248>", probe_lds<67248>, 512);
