@@ -554,7 +554,22 @@ int lfg_gp_lnlike(const double* x, const double* ye, const double* res, int W,
  * (point, draw, first + vector, j), j = 0, 1: process noise of g and h,
  * j = 2: the datum's noise; a draw depends on nothing else, so a batch cut
  * into several calls (first = the index of each call's row 0) gives the same
- * bits.  W * S <= 2^30.
+ * bits.  W * S <= 2^30.  To the letter (tests/gp_sample_double.py is the
+ * host double of it):
+ *   key      (seed's low word, seed's high word)
+ *   point    the index on the merged grid (0 .. n - 1, data and test points
+ *            alike), not the index among the data or among t
+ *   first + vector  the unsigned 32-bit sum
+ *   normals  a block's words (w0, w1, w2, w3) give two by Box-Muller, with
+ *            u53(a, b) = ((a >> 5) 2^26 + (b >> 6)) / 2^53: the radius is
+ *            sqrt(-2 ln(1 - u53(w0, w1))), the angle 2 pi u53(w2, w3); the
+ *            first normal is radius * cos, the second radius * sin
+ *   j = 0    (z0, z1): g's stationary start at point 0, its step noise
+ *            chol(Q) (z0, z1) after
+ *   j = 1    (z2, z3): the same for h, and h's fresh stationary start at a
+ *            block's first point
+ *   j = 2    its first normal is eps (ye * z4 at a datum); its second is
+ *            unused
  * LFG_E_ARGS (and no launch) on null or short arguments, a refused shape, or
  * ws_bytes below the size function's value.
  */

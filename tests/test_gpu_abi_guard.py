@@ -449,6 +449,21 @@ def _sample_verify(D, A):
         mu, _ = gs.dense_predict(x, ye, res[k], *D["hyp"][k], D["blocks"][k], t)
         reach = 8.0 * np.sqrt(D["hyp"][k][0] + D["hyp"][k][1])
         assert np.max(np.abs(draws[k][:, D["it"]] - mu[None, :])) <= reach, k
+    # draw for draw against the host double (tests/gp_sample_double.py) on the whole merged grid, at the GP
+    # bar: row k of the first call is keyed 2 + k, row k of the tail 3 + k
+    from tests import gp_sample_double as gd
+    if "double" not in D:
+        D["double"] = np.stack([gd.draws(D["x"], D["ye"], D["obs"], D["res"][k], D["hyp"][k], D["blocks"][k], 3, 12345,
+                                         2, k) for k in range(D["W"])])
+        tail = np.stack([gd.draws(D["x"], D["ye"], D["obs"], D["res"][k], D["hyp"][k], D["blocks"][k], 3, 12345, 3,
+                                  k - 1) for k in range(1, D["W"])])
+        assert np.array_equal(tail, D["double"][1:])
+    tail_draws = A.tensor("draws.tail").cpu().numpy()
+    for k in range(D["W"]):
+        bar = gs.BAR * np.sqrt(D["hyp"][k][0] + D["hyp"][k][1])
+        assert np.max(np.abs(draws[k] - D["double"][k])) <= bar, k
+        if k:
+            assert np.max(np.abs(tail_draws[k - 1] - D["double"][k])) <= bar, k
 
 
 # the GP posterior entry points answer a short scratch with LFG_E_ARGS (the header's rule for them)
