@@ -51,7 +51,7 @@ double disc_boundary(int i, const Pair& G)
 {
     const double r = G.rwd_a + i * ((G.rdisc_a - G.rwd_a) / NDISC_R);
     const double ex = 2.0 - G.dexp;
-    const double lr = std::log(r / G.rwd_a);  // lfg.hip disc_boundary: the integral from the inner edge
+    const double lr = std::log(r / G.rwd_a);  // lfg_k_elements.hpp: disc_boundary, the integral from the inner edge
     return (std::fabs(ex) < 1e-10) ? lr : std::pow(G.rwd_a, ex) * std::expm1(ex * lr) / ex;
 }
 

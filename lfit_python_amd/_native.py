@@ -30,8 +30,8 @@ SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "
            os.path.join(_HERE, "csrc", "lfg_physpar.hip"),  # physical parameters from chain rows (lfg_physpar.h)
            os.path.join(_HERE, "csrc", "lfg_wd.hip"),  # the white-dwarf atmosphere fit (lfg_wd.h)
            os.path.join(_HERE, "csrc", "lfg_chain.hip")]  # a chain's summary (lfg_chain.h)
-# k_pair's fold and LONG instantiations: lfg.hip again, compiled on its own
-# without machine LICM (the reason: lfg.hip, lfg_pair_launch_split)
+# k_pair's fold and LONG instantiations: the kernels header, compiled a second
+# time without machine LICM (the reason: lfg_kernels.hpp, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
 SPLIT_FLAGS = ["-mllvm", "-disable-machine-licm"]
 # every header a unit can include: whatever csrc/ holds, and the C ABI

@@ -1,5 +1,6 @@
 // lfg_diag.hpp -- the one rule for one-unit diagnostic builds, seen by lfg.hip
-// and lfg_pair_split.hip alike.  The diagnostic device globals are per-unit
+// and lfg_pair_split.hip alike (through lfg_kernels.hpp: the kernels header,
+// compiled a second time without machine LICM).  The diagnostic device globals are per-unit
 // copies (anonymous namespace), so a kernel compiled in lfg_pair_split.hip
 // would write a copy that lfg_debug_* / lfg_diag_iters, in lfg.hip, never
 // read.  LFG_ONE_TU keeps every kernel in lfg.hip; it is set whenever a

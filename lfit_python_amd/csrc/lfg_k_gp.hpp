@@ -1,10 +1,9 @@
 // lfg_k_gp.hpp -- the GP tree kernels k_gp_dcp and k_gp_like, and the two
 // combines k_combine_walkers and k_combine.  Needs before it: lfg_device.hpp
 // (findphi_fast, element_interval, eggleton), lfg_philox.hpp (draw, u53),
-// and lfg.hip's sections k_elements (prior_rejects), k_lnlike (LikeArgs,
+// lfg_k_elements.hpp (prior_rejects), lfg_k_lnlike.hpp (LikeArgs,
 // combine_walker, combine_after) and lfg_k_pair.hpp (DCP_LANES, DCP_NTHETA).
-// Included in lfg.hip's anonymous namespace, not in lfg_pair_split.hip's
-// unit (LFG_NOLICM_TU).
+// Included by lfg.hip only, in its anonymous namespace.
 #pragma once
 
 // -------------------------------------------------------------- k_gp_dcp

@@ -1,8 +1,8 @@
 // lfg_k_misc.hpp -- k_gp, k_wdphases and k_roche, and the host's launch_ok
 // and run_front (k_setup then k_elements).  Needs before it: lfg_device.hpp
-// (Roche, GPFilter, wdphases) and lfg.hip's sections k_setup (SetupArgs, the
-// kernel) and k_elements (ElemSpec, NUNIQ, the kernel).  Included in lfg.hip's
-// anonymous namespace, not in lfg_pair_split.hip's unit (LFG_NOLICM_TU).
+// (Roche, GPFilter, wdphases), lfg_k_setup.hpp (SetupArgs), lfg_k_elements.hpp
+// (ElemSpec, NUNIQ) and lfg_k_front.hpp (the kernels k_setup and k_elements).
+// Included by lfg.hip only, in its anonymous namespace.
 #pragma once
 
 // ------------------------------------------------------ k_gp, k_wdphases

@@ -1,8 +1,9 @@
 // lfg_k_pair.hpp -- k_pair: PairHot, PairArgs, fill_hot, PairSink and the
 // point-major sinks, the LONG tables (lfg_k_pair_long.hpp, included where
-// they stood) and the kernel.  Needs before it: lfg.hip's sections k_setup,
-// k_elements and k_lnlike.  Included in lfg.hip's anonymous namespace, where
-// the section stood, and so in lfg_pair_split.hip's unit too (LFG_NOLICM_TU).
+// they stood) and the kernel.  Needs before it: lfg_k_setup.hpp,
+// lfg_k_elements.hpp and lfg_k_lnlike.hpp.  Included by lfg_kernels.hpp, in
+// its anonymous namespace, and so in both lfg.hip's and lfg_pair_split.hip's
+// units.
 #pragma once
 
 // ------------------------------------------------------------------ k_pair

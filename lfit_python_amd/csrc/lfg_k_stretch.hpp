@@ -1,7 +1,7 @@
 // lfg_k_stretch.hpp -- the stretch-move sampler's kernels: k_propose,
 // k_accept, k_accept_regen, k_apply_verdicts, k_verdict.  Needs
-// lfg_philox.hpp before it; included in lfg.hip's anonymous
-// namespace, not in lfg_pair_split.hip's unit (LFG_NOLICM_TU).
+// lfg_philox.hpp before it; included by lfg.hip only, in its anonymous
+// namespace.
 #pragma once
 
 // ------------------------------------------------------- stretch-move sampler

@@ -1,9 +1,9 @@
-// lfg_pair_split.hip -- k_pair's fold and LONG instantiations, compiled from
-// lfg.hip's own source with -mllvm -disable-machine-licm (why: the comment
-// at lfg_pair_launch_split in lfg.hip).  Only the kernels this launcher
-// instantiates are taken from here; lfg.hip's C ABI is compiled out.
-#define LFG_NOLICM_TU 1
-#include "lfg.hip"
+// lfg_pair_split.hip -- k_pair's fold and LONG instantiations: the kernels
+// header, compiled a second time without machine LICM (-mllvm
+// -disable-machine-licm; why: the comment at lfg_pair_launch_split in
+// lfg_kernels.hpp).  The header defines no __global__ but the k_lnlike and
+// k_pair templates, so only the kernels this launcher instantiates come out.
+#include "lfg_kernels.hpp"
 
 #ifndef LFG_ONE_TU
 void lfg_pair_launch_split(int variant, unsigned grid, hipStream_t st, const void* args)

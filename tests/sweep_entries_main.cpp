@@ -36,7 +36,7 @@ struct Windows {
     std::vector<int> cell;
 };
 
-// cell[g] = #{p : ci(v_p) < g}, ci as cell_of clamps it (lfg.hip: build_cells)
+// cell[g] = #{p : ci(v_p) < g}, ci as cell_of clamps it (lfg_k_lnlike.hpp: build_cells)
 void build_cells(Windows& W, int m)
 {
     W.cell.assign(LIKE_NC + 1, 0);
@@ -85,7 +85,7 @@ Windows make_windows(int set, int m, std::mt19937_64& rng)
     return W;
 }
 
-int ring_sqrt(int u)  // lfg.hip: wd_ring_of
+int ring_sqrt(int u)  // lfg_k_elements.hpp: wd_ring_of
 {
     int ir = int(std::sqrt(u * 0.5));
     if (2 * (ir + 1) * (ir + 1) <= u) ++ir;
@@ -93,7 +93,7 @@ int ring_sqrt(int u)  // lfg.hip: wd_ring_of
     return ir;
 }
 
-int ring_sqrtf(int u)  // lfg.hip: uring
+int ring_sqrtf(int u)  // lfg_k_lnlike.hpp: uring
 {
     if (u >= 200) return 10 + (u - 200) / 25;
     int r = int(std::sqrt(float(u) * 0.5f));

@@ -4,7 +4,7 @@ the oracle.
 After the phase barrier wave i < 6 scans difference array i in place, lane l
 owning the run [l R, min((l + 1) R, m)) with R = ceil(m / 64), and a wave whose
 first thread lies past the last point does nothing but reach the barriers
-(lfg.hip: run_scan; lfg_k_pair.hpp: k_pair).  The point counts below are where that code
+(lfg_k_lnlike.hpp: run_scan; lfg_k_pair.hpp: k_pair).  The point counts below are where that code
 changes its shape:
 
     n = 2            R = 1, 62 empty lanes, seven idle waves

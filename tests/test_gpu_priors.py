@@ -1,5 +1,5 @@
 """GPU: the prior lanes of k_setup (prior_lane, bspot_lane and the setup
-lane's Roche checks in lfg.hip) at every prior's edges, per prior type,
+lane's Roche checks in lfg_k_setup.hpp: setup_any) at every prior's edges, per prior type,
 against the host double tests/prior_double.py, which tests/test_prior_double.py
 pins against the reference's own ln_prior first.
 

@@ -209,12 +209,13 @@ def test_source_hash_covers_every_included_header(tmp_path, monkeypatch):
 
 
 def test_split_unit_compiles_k_pairs_three_instantiations_only(tmp_path):
-    """lfg_pair_split.hip compiles lfg.hip a second time (LFG_NOLICM_TU) for
-    k_pair<false, FOLD, LONG>, FOLD or LONG set, and for nothing else: a
-    kernel added to lfg.hip or a header of its without a guard would come out
-    of both units, twice in the library.  So the two units' kernel sets are
-    disjoint and the main unit holds the kernels the split unit leaves out.
-    And no other file includes lfg.hip."""
+    """lfg_pair_split.hip compiles the kernels header lfg_kernels.hpp a second
+    time, without machine LICM, for k_pair<false, FOLD, LONG>, FOLD or LONG
+    set, and for nothing else: a non-template __global__ added to that header
+    or to a section header of its would come out of both units, twice in the
+    library.  So the two units' kernel sets are disjoint and the main unit
+    holds the kernels the split unit leaves out.  And no file includes lfg.hip,
+    the host unit: the split unit includes the kernels header."""
     def kernels_of(source, extra, name):
         out = tmp_path / name
         subprocess.run(["hipcc"] + [f for f in _native.FLAGS if f != "-shared"] + extra +
@@ -237,9 +238,10 @@ def test_split_unit_compiles_k_pairs_three_instantiations_only(tmp_path):
     csrc = os.path.dirname(_native.SPLIT_SOURCE)
     sources = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".hpp", ".h"))]
     assert os.path.basename(_native.SPLIT_SOURCE) in sources and len(sources) >= 10
+    host_unit = '#include "%s"' % os.path.basename(_native.SOURCES[0])
     for name in sources:
-        if name != os.path.basename(_native.SPLIT_SOURCE):
-            assert '#include "lfg.hip"' not in open(os.path.join(csrc, name)).read(), name
+        assert host_unit not in open(os.path.join(csrc, name)).read(), name
+    assert '#include "lfg_kernels.hpp"' in open(_native.SPLIT_SOURCE).read()
 
 
 def test_foreign_library_refused(tmp_path):

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Experiment/diagnostic builds of liblfg_hip.so: build/exp/liblfg_<name>.so
 # with extra compile flags, loaded through LFG_LIB (lfit_python_amd/_native.py).
-# usage: tools/build_exp.sh <name> [-DFLAG ...]   (LFG_SRC=<file>: another lfg.hip; it includes
-#        the lfg_k_*.hpp headers by name, so it sits in lfit_python_amd/csrc/ next to them)
+# usage: tools/build_exp.sh <name> [-DFLAG ...]   (LFG_SRC=<file>: another host unit in place of
+#        lfg.hip; it includes lfg_kernels.hpp and the lfg_k_*.hpp headers by name, so it must sit
+#        in lfit_python_amd/csrc/ next to them; the split unit is lfg_pair_split.hip as it stands)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift

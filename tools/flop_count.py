@@ -79,7 +79,7 @@ def walkers(config, n, seed=20261015):
 
 def prior_sum_flops(types, chunk=16):
     """Prior.ln_prob sum of a prior lane from the tree's constants
-    (lfg_tree.prior_c; lfg.hip prior_lane): per parameter gauss
+    (lfg_tree.prior_c; lfg_k_setup.hpp: prior_lane): per parameter gauss
     (v - p1) c1 and fma(-z/2, z, c0) = 5, plus the running add; log_uniform
     one product multiply, mod_jeff also v + p1; per chunk one log and one sub."""
     per = {0: 6, 1: 6, 2: 1, 3: 2, 4: 3}

@@ -2,7 +2,7 @@
 // walker-eclipse evaluation (MODEL_SPEC.md section 11).  The device functions
 // of lfit_python_amd/csrc/lfg_device.hpp are compiled for the host over the
 // counting type of flop.hpp (`double` -> F64), and the lane bodies of k_setup
-// and k_elements (lfg.hip) are restated around them, so the counts are those
+// and k_elements (lfg_k_setup.hpp: setup_any; lfg_k_elements.hpp: element_lane) are restated around them, so the counts are those
 // of the kernels' own arithmetic, iteration by iteration, on given parameter
 // sets.  Built and driven by tools/flop_count.py; tooling only.
 #include <algorithm>
@@ -43,7 +43,7 @@ int lfc_count_pair(const double* pin, int np, long long* out)
     for (int k = 0; k < 18; ++k) p[k] = F64(k < np ? pin[k] : 0.0);
     if (np == 14) { p[14] = 2.0; p[15] = 1.0; p[16] = 90.0; p[17] = 0.0; }
 
-    // ---- k_setup setup lane (lfg.hip k_setup, pair part)
+    // ---- k_setup setup lane (lfg_k_setup.hpp: setup_any, pair part)
     FlopCtr c0 = snap();
     Roche R;
     if (roche_init(R, p[4]) != ST_OK) return 1;

@@ -1,7 +1,7 @@
 """Counted FP64 work of k_lnlike per walker-eclipse pair (MODEL_SPEC.md 11.2).
 
 k_lnlike is restated here block phase by block phase (lfit_python_amd/csrc/
-lfg.hip, k_lnlike<MODE, SUB>) as counts of the FP64 operations each thread
+lfg_k_lnlike.hpp: k_lnlike<MODE, SUB>) as counts of the FP64 operations each thread
 executes, with MODEL_SPEC 11's rules: add, sub, mul 1; fma 2; div, sqrt,
 rcp 1; each transcendental 1 (sincospi = sin + cos = 2); compares,
 selects, min / max, conversions, integer and fixed-point (int64) work 0.
@@ -25,7 +25,7 @@ NWD, NDISC, NBS, NDONOR = 400, 1000, 100, 400
 NI = (NWD + NDISC + LIKE_THREADS - 1) // LIKE_THREADS  # sweep slots per thread
 TCELLS = 256
 
-# ---- once per pair (prologue, lfg.hip k_lnlike before the tile loop)
+# ---- once per pair (prologue, lfg_k_lnlike.hpp: k_lnlike before the tile loop)
 C_RING = 4          # wd_ring_weight: fma(kWdA, 1 - ul, kWdB * ul), 10 lanes
 C_DONOR_NORM = 5    # dn = max(-s vy + c vz, 0) (3), vs = |vx| + |vy| + |vz| (2), 400 lanes
 C_WAVESUM = 6       # one DPP wave sum: 6 adds per lane
@@ -112,7 +112,7 @@ def count_pair(x, w, nsub, a, b, sa, sb, donor, inc_deg, phi0, gp=False):
     f = prologue()
     parts = {"prologue": f, "tables": 0.0, "tiles_thread": 0.0, "tiles_point": 0.0, "wd_disc": 0.0,
              "spot_donor": 0.0, "subbins": 0.0}
-    if sub:  # table build (lfg.hip k_lnlike, `if (TAB)`)
+    if sub:  # table build (lfg_k_lnlike.hpp: k_lnlike, `if (TAB)`)
         ft = LIKE_THREADS * C_TAB_THR + n * (C_TAB_PT0 + C_TAB_SUB * S)
         alive = hw > 0
         ft += int(alive.sum()) * (C_TAB_DON + 2 * 2 * C_TCELL) + int(secl.sum()) * (2 + 2 * 2 * C_TCELL)

@@ -1,8 +1,10 @@
 // Diagnostic: resident blocks per CU of the lfg kernels (occupancy API) and
 // of probe kernels that isolate the LDS and VGPR limits.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include tools/occupancy.hip -o build/occupancy
-#define LFG_ONE_TU 1  // every kernel in this unit: there is no lfg_pair_split.hip to link
-#include "../lfit_python_amd/csrc/lfg.hip"
+#include "../lfit_python_amd/csrc/lfg_kernels.hpp"
+namespace {
+#include "../lfit_python_amd/csrc/lfg_k_front.hpp"  // k_setup, k_elements
+}
 #include <cstdio>
 
 template <int LDS_BYTES>
