@@ -25,7 +25,7 @@ def build(out=None, march="x86-64-v3", extra=()):
            "-I", HERE, "-I", os.path.join(HERE, "shim"), "-I", os.path.join(ROOT, "lfit_python_amd", "csrc"),
            "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp"),
            os.path.join(HERE, "lfg_cpu_physpar.cpp"), os.path.join(HERE, "lfg_cpu_wd.cpp"),
-           os.path.join(HERE, "lfg_cpu_chain.cpp")]
+           os.path.join(HERE, "lfg_cpu_chain.cpp"), os.path.join(HERE, "lfg_cpu_limbdark.cpp")]
     subprocess.run(cmd, check=True)
     return out
 
@@ -156,6 +156,27 @@ class CpuPort:
         if rc != 0:
             raise ValueError("lfg_cpu_physpar: code %d" % rc)
         return np.ascontiguousarray(out.T), model, st
+
+    def limbdark(self, logg, teff, tables, ld=1, n=None, nthreads=0):
+        """lfg_cpu_limbdark: (table [n, 25], status [n]).  tables: a
+        lfit_python_amd.limbdark.LDTables; logg and teff are read at element
+        i * ld (n rows; default: their length with ld = 1)."""
+        from lfit_python_amd import _native
+        logg, teff = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (logg, teff))
+        n = teff.size if n is None else int(n)
+        assert all(n == 0 or a.size > (n - 1) * ld for a in (logg, teff))
+        out = np.empty((n, 25))
+        st = np.empty(n, dtype=np.int32)
+        f = self.lib.lfg_cpu_limbdark
+        f.restype = ctypes.c_int
+        f.argtypes = [_dp, _dp, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_native.LfgLdTables), _dp, _ip,
+                      ctypes.c_int]
+        T = tables.host_struct()
+        rc = f(logg.ctypes.data_as(_dp), teff.ctypes.data_as(_dp), int(ld), n, ctypes.byref(T),
+               out.ctypes.data_as(_dp), st.ctypes.data_as(_ip), int(nthreads))
+        if rc != 0:
+            raise ValueError("lfg_cpu_limbdark: code %d" % rc)
+        return out, st
 
     def wd_lnprob(self, theta, model, ld=None, n=None, nthreads=0):
         """lfg_cpu_wd_lnprob: (lnp [n], lnlike [n], mags [n, B], status [n]).

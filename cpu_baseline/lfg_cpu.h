@@ -14,6 +14,7 @@
 #include "lfg_physpar.h"
 #include "lfg_wd.h"
 #include "lfg_chain.h"
+#include "lfg_limbdark.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -66,6 +67,12 @@ int lfg_cpu_chain_stats(const double* base, long long steps, long long W, int C,
 int lfg_cpu_chain_clip(const long long* n, const double* m2, const double* med,
                        long long med_ld, double sigma, const double* win_in,
                        double* win_out, int C);
+
+/* lfg_limbdark's twin (include/lfg_limbdark.h; limbdark.py ld()): the same
+ * arguments on host pointers, the tables' arrays included */
+int lfg_cpu_limbdark(const double* logg, const double* teff, size_t ld, int n,
+                     const lfg_ld_tables* tab, double* out, int* status,
+                     int nthreads);
 
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */

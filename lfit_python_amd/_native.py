@@ -29,7 +29,8 @@ SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "
            os.path.join(_HERE, "csrc", "lfg_gp_predict.hip"),  # the GP smoother and conditional sampler
            os.path.join(_HERE, "csrc", "lfg_physpar.hip"),  # physical parameters from chain rows (lfg_physpar.h)
            os.path.join(_HERE, "csrc", "lfg_wd.hip"),  # the white-dwarf atmosphere fit (lfg_wd.h)
-           os.path.join(_HERE, "csrc", "lfg_chain.hip")]  # a chain's summary (lfg_chain.h)
+           os.path.join(_HERE, "csrc", "lfg_chain.hip"),  # a chain's summary (lfg_chain.h)
+           os.path.join(_HERE, "csrc", "lfg_limbdark.hip")]  # limb-darkening coefficients (lfg_limbdark.h)
 # k_pair's fold and LONG instantiations: the kernels header, compiled a second
 # time without machine LICM (the reason: lfg_kernels.hpp, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -39,7 +40,8 @@ HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join
                  if f.endswith((".hpp", ".h"))) + [os.path.join(REPO, "include", "lfg.h"),
                                                    os.path.join(REPO, "include", "lfg_physpar.h"),
                                                    os.path.join(REPO, "include", "lfg_wd.h"),
-                                                   os.path.join(REPO, "include", "lfg_chain.h")]
+                                                   os.path.join(REPO, "include", "lfg_chain.h"),
+                                                   os.path.join(REPO, "include", "lfg_limbdark.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 
@@ -137,6 +139,18 @@ class LfgWdModel(ctypes.Structure):
 EXPORTS_CHAIN = ("lfg_chain_workspace_size", "lfg_chain_tile_rows", "lfg_chain_hist_tile", "lfg_chain_stats",
                  "lfg_chain_clip")
 CHAIN_MAX_C, CHAIN_MAX_NQ = 4096, 8  # LFG_CHAIN_* (include/lfg_chain.h)
+
+# include/lfg_limbdark.h: limb-darkening coefficients, a set of its own too
+EXPORTS_LIMBDARK = ("lfg_limbdark", "lfg_limbdark_lanes")
+LD_NBAND, LD_NCOEF, LD_NCOL, LD_MAX_KNOTS = 5, 5, 25, 64  # LFG_LD_* (include/lfg_limbdark.h)
+ST_LD_CLAMPED = 7  # LFG_ST_LD_CLAMPED
+STATUS_TEXT_LIMBDARK = {0: "ok", 5: "non-finite logg or teff", 7: "logg or teff outside the tables: clamped"}
+
+
+class LfgLdTables(ctypes.Structure):
+    """ctypes mirror of struct lfg_ld_tables (include/lfg_limbdark.h)."""
+    _fields_ = [("tx", ctypes.c_void_p), ("ty", ctypes.c_void_p), ("nx", ctypes.c_int), ("ny", ctypes.c_int),
+                ("c", ctypes.c_void_p)]
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -345,6 +359,10 @@ def lib():
                                       vp, vp, vp, vp, sz, vp]
         L.lfg_chain_clip.restype = ip
         L.lfg_chain_clip.argtypes = [vp, vp, vp, i64, f64, vp, vp, ip, vp]
+        L.lfg_limbdark.restype = ip
+        L.lfg_limbdark.argtypes = [vp, vp, sz, ip, ctypes.POINTER(LfgLdTables), vp, vp, vp]
+        L.lfg_limbdark_lanes.restype = ip
+        L.lfg_limbdark_lanes.argtypes = []
         if hasattr(L, "lfg_set_layout"):  # (older experiment builds lack it)
             L.lfg_set_layout.restype = ip
             L.lfg_set_layout.argtypes = [ip]

@@ -3,8 +3,8 @@
 # the library's gfx950 code, from the compiler's kernel-resource-usage
 # remarks: lfg.hip, then lfg_pair_split.hip (k_pair's fold and LONG
 # instantiations, compiled without machine LICM as the library builds them),
-# then lfg_pt.hip (the parallel-tempering kernels) and lfg_gp_predict.hip (the
-# GP smoother).
+# then lfg_pt.hip (the parallel-tempering kernels), lfg_gp_predict.hip (the
+# GP smoother) and lfg_limbdark.hip (the limb-darkening coefficients).
 #   tools/kernel_resources.sh [extra hipcc flags]   -> stdout
 set -e
 cd "$(dirname "$0")/.."
@@ -19,3 +19,4 @@ unit lfg.hip "$@"
 unit lfg_pair_split.hip -mllvm -disable-machine-licm "$@"
 unit lfg_pt.hip "$@"
 unit lfg_gp_predict.hip "$@"
+unit lfg_limbdark.hip "$@"
