@@ -77,6 +77,13 @@ class CpuPort:
             lnp[:] = -np.inf
         return lnp, used
 
+    def gp_dcp(self, q, dphi, rwd):
+        """the port's dist_cp of (q, dphi, rwd) (MODEL_SPEC 10.3), NaN on failure"""
+        f = self.lib.lfc_gp_dcp
+        f.restype = ctypes.c_double
+        f.argtypes = [ctypes.c_double] * 3
+        return f(float(q), float(dphi), float(rwd))
+
     # ---- the lfg_cpu_* twins (cpu_baseline/lfg_cpu.h) of lfg_flux,
     # lfg_lnlike and lfg_lnprob: host arrays, the same argument meaning
     def flux(self, pars, x, w, nsub=1, nthreads=0):

@@ -548,6 +548,19 @@ int lfc_lnprob_batch(const double* walkers, int W, int ndim, int E, const int* g
                                prior_p1, prior_p2, prior_norm, roche_priors, nullptr, nullptr, nullptr, lnp, nthreads);
 }
 
+// gp_dcp on its own, as the unfilled cache below reaches it (findi, then the
+// limb circle): dist_cp of (q, dphi, rwd), NaN on any failure.  For tests.
+double lfc_gp_dcp(double q, double dphi, double rwd)
+{
+    Pair G{};
+    double inc;
+    if (roche_init(G.R, q) != ST_OK || findi_fast(G.R, dphi, inc) != ST_OK) return NAN;
+    G.inc = inc;
+    G.s = std::sin(inc * DEG);
+    G.c = std::cos(inc * DEG);
+    return gp_dcp(G, dphi, rwd);
+}
+
 // the same with a GP likelihood per eclipse (gp_gather [E][3]: ln_ampin,
 // ln_ampout, ln_tau; gp_base [E][4]: the changepoint cache q, dphi, rwd,
 // dist_cp; gp_ecl [E][2]: first and last eclipse number); all null: chi^2
@@ -566,13 +579,7 @@ int lfc_lnprob_batch_gp(const double* walkers, int W, int ndim, int E, const int
         for (int e = 0; e < E; ++e) {
             double* B = &base[4 * e];
             if (std::isfinite(B[3])) continue;
-            Pair G{};
-            double inc;
-            if (roche_init(G.R, B[0]) != ST_OK || findi_fast(G.R, B[1], inc) != ST_OK) continue;
-            G.inc = inc;
-            G.s = std::sin(inc * DEG);
-            G.c = std::cos(inc * DEG);
-            B[3] = gp_dcp(G, B[1], B[2]);
+            B[3] = lfc_gp_dcp(B[0], B[1], B[2]);
         }
         gp_base = base.data();
     }

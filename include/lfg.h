@@ -511,7 +511,11 @@ int lfg_pt_swap(const double* pos_in, double* pos_out, double* lnl,
  * Batched trm.roche.wdphases(q, iangle, r1, ntheta) (CVModel.py:564): third
  * and fourth contact phases of a sphere of radius r1 at the white dwarf.
  * q, inc (degrees), r1, phi3, phi4, status: [dev] n.  phi3[i] and phi4[i]
- * of a row whose status is not LFG_ST_OK are NaN.
+ * of a row whose status is not LFG_ST_OK are NaN.  Per row, first match:
+ * LFG_ST_BAD_Q (q <= 0 or not finite), LFG_ST_BAD_GEOMETRY (r1 <= 0 or NaN),
+ * LFG_ST_BAD_DPHI (the white dwarf's centre is not eclipsed at inc, or no
+ * limb point is).  phi3 may be negative at grazing inclinations.  ntheta < 1
+ * is refused as a whole: LFG_E_ARGS, nothing written.
  */
 int lfg_wdphases(const double* q, const double* inc, const double* r1, int n,
                  int ntheta, double* phi3, double* phi4, int* status,

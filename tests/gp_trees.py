@@ -17,6 +17,10 @@ number of walkers a GPU test hands to one call: the walkers go through in
 consecutive chunks of that size (chunks()), so that the launch has the
 case's walker count (a lone pair, a dead second pair in the last wave) while
 every case still holds all five designated rows.
+
+rule_case(oracle, name) -> (model, walkers): the rule family at the end of
+this file, the 120 % cache rule at its edges with data laddered around every
+block edge the independent double's dist_cp gives.
 """
 import numpy as np
 
@@ -203,3 +207,124 @@ def check_case(name, walkers, ref):
     assert 4 * fin.sum() >= 3 * len(ref), (name, fin)
     assert fin[list(FINITE_ROWS)].all(), (name, fin)
     assert np.isneginf(ref[ROW_OUT]), (name, ref[ROW_OUT])
+
+
+# ---------------------------------------------------------------- the rule family
+# MODEL_SPEC 10.3's cache rule |base - v| / v > 1.2 at its edges, through the
+# likelihood.  |B - v| / v = B / v - 1 for v < B, so the threshold is v = B / 2.2:
+# a divisor of 2.2 (1 + 1e-3) trips the rule (1.2022), 2.2 (1 - 1e-3) does not
+# (1.1978); no row lies within 1e-6 relative of the threshold, whose own
+# verdict depends on a rounding.  v > B can never trip (|B - v| / v < 1).
+#
+# Every dist_cp here is the independent double's (tests/wdphases_double.py),
+# recorded in tests/golden/wdphases_double.npz under rule_*; the blocks are the
+# double's Python rule, not oracle.gp_base_dcp.  Each leaf's phases are 64
+# random ones plus a ladder: for the cached dist_cp and for every tripped
+# row's own, at both block edges inside the data (-dcp + phi0, dcp + phi0),
+# points at edge +- RUNGS.  The smallest rung is 100 PHASE_ATOL, so a dist_cp
+# off by more than 1e-8 moves a datum across an edge.
+RULE_CASES = ("rule_e1", "rule_e3")
+RULE_CALL_W = {"rule_e1": 12, "rule_e3": 7}    # e3: 21 pairs, k_gp_dcp's blocks of 4 mix pending and cached pairs
+RULE_LEAVES = {"rule_e1": ("0",), "rule_e3": ("0", "1", "2")}
+RUNGS = (1e-8, 1e-7, 1e-6, 1e-5, 1e-4)
+TRIP, KEEP = 2.2 * (1.0 + 1e-3), 2.2 * (1.0 - 1e-3)
+RULE_ROWS = ("trip_q", "keep_q", "high_q", "trip_dphi", "keep_dphi", "high_dphi", "trip_rwd", "keep_rwd", "high_rwd",
+             "two", "hyper", "out")
+RULE_TRIPPED = ("trip_q", "trip_dphi", "trip_rwd", "two")
+RULE_FINITE = RULE_ROWS[:-1]
+HIGH = {"q": 0.49, "rwd": 0.0999}   # the priors' upper ends (synthetic.CORE); dphi: findphi(q, 90) - 1e-5
+RULE_GOLDEN = "wdphases_double.npz"
+
+
+def rule_values(high_dphi=None):
+    """name -> (q, dphi, rwd) of the rows the double's dist_cp is recorded
+    for (the base, the tripped rows, the rows just short of tripping)"""
+    q, dphi, rwd = (float(synthetic.CORE[k].split()[0]) for k in ('q', 'dphi', 'rwd'))
+    out = {"base": (q, dphi, rwd),
+           "trip_q": (q / TRIP, dphi, rwd), "trip_dphi": (q, dphi / TRIP, rwd), "trip_rwd": (q, dphi, rwd / TRIP),
+           "two": (q, dphi / 2.3, rwd / 2.3),
+           "keep_q": (q / KEEP, dphi, rwd), "keep_dphi": (q, dphi / KEEP, rwd), "keep_rwd": (q, dphi, rwd / KEEP)}
+    if high_dphi is not None:
+        out.update(high_q=(HIGH["q"], dphi, rwd), high_dphi=(q, high_dphi, rwd), high_rwd=(q, dphi, HIGH["rwd"]))
+    return out
+
+
+def rule_dcp():
+    """name -> the double's recorded dist_cp, held to rule_values() bit for bit"""
+    import os
+    d = np.load(os.path.join(os.path.dirname(__file__), "golden", RULE_GOLDEN))
+    vals = rule_values()
+    out = {}
+    for k, name in enumerate(d["rule_name"]):
+        assert (d["rule_q"][k], d["rule_dphi"][k], d["rule_rwd"][k]) == vals[str(name)], name
+        out[str(name)] = float(d["rule_dcp"][k])
+    assert set(out) == set(vals)
+    return out
+
+
+def rule_phases(label, dcp, rng):
+    phi0 = synthetic._EVALS[label][1][7]
+    x = [_uniform_sorted(rng, 64)]
+    for name in ("base",) + RULE_TRIPPED:
+        for edge in (-dcp[name] + phi0, dcp[name] + phi0):
+            x.append([edge + sg * r for r in RUNGS for sg in (-1.0, 1.0)])
+    x = np.sort(np.concatenate(x))
+    assert x.size == 64 + 20 * 5 and np.min(np.diff(x)) >= 0.9 * RUNGS[0]
+    return x
+
+
+def rule_case(oracle, name):
+    """(model, walkers [12, ndim]) of a rule tree; the rows are RULE_ROWS"""
+    dcp = rule_dcp()
+    rng = np.random.default_rng(300 + RULE_CASES.index(name))
+    leaves = RULE_LEAVES[name]
+    # e1: a simple bright-spot leaf; e3: complex leaves
+    model = build_tree(oracle, [(lab, rule_phases(lab, dcp, rng)) for lab in leaves], complex_bs=len(leaves) > 1,
+                       seed=16)
+    names = model.dynasty_par_names
+    col = lambda prefix: [i for i, n in enumerate(names) if n.startswith(prefix)]  # noqa: E731
+    p0 = np.array(model.dynasty_par_vals)
+    vals = rule_values(high_dphi=oracle.findphi(p0[col('q_')[0]], 90.0) - 1e-5)
+    walk = np.tile(p0, (len(RULE_ROWS), 1))
+    for row, rname in enumerate(RULE_ROWS):
+        if rname in vals:
+            for nm, v in zip(('q', 'dphi', 'rwd'), vals[rname]):
+                walk[row, col(nm + '_')[0]] = v
+            # the Roche prior wants rwd / 3 <= scale <= 3 rwd (SimpleEclipse.ln_prior)
+            walk[row, col('scale_')] = walk[row, col('rwd_')[0]]
+    hrng = np.random.default_rng(400 + RULE_CASES.index(name))
+    row = RULE_ROWS.index("hyper")
+    walk[row, col('ln_ampin_gp')[0]] = hrng.uniform(*LN_AMP)
+    walk[row, col('ln_ampout_gp')[0]] = hrng.uniform(*LN_AMP)
+    walk[row, col('ln_tau_gp')[0]] = hrng.uniform(*LN_TAU)
+    walk[RULE_ROWS.index("out"), col('dFlux_')[0]] = 0.3     # outside uniform(0.001, 0.2): -inf
+    return model, walk
+
+
+def rule_blocks(tree, e, v, dcp):
+    """the blocks of eclipse e for walker v by the double's rule and recorded
+    dist_cp values (dcp: rule_dcp()); a tripped walker must be a recorded one"""
+    from tests import wdphases_double as wd
+    p = eclipse_pars(tree, e, v)
+    q, dphi, rwd, phi0 = p[4], p[5], p[8], p[13]
+    base = tuple(tree.gp_base[e, :3]) + (dcp["base"],)
+    assert base[:3] == rule_values()["base"]
+    own = None
+    if wd.tripped(base, q, dphi, rwd):
+        own = [dcp[n] for n, val in rule_values().items() if val == (q, dphi, rwd)][0]
+    return np.array(wd.blocks(base, q, dphi, rwd, phi0, int(tree.gp_ecl[e, 0]), int(tree.gp_ecl[e, 1]), own=own))
+
+
+def rule_reference(oracle, tree, walk, dcp, nsub=1, blocks_fn=None):
+    """lnlike_e [W, E] on the host: y - oracle.flux through the dense GP with
+    the double's blocks; NaN where the flux fails"""
+    out = np.full((len(walk), tree.E), np.nan)
+    for i, v in enumerate(walk):
+        for e in range(tree.E):
+            sl = slice(tree.offsets[e], tree.offsets[e + 1])
+            st, f = oracle.flux(eclipse_pars(tree, e, v), tree.x[sl], tree.w[sl], nsub=nsub)
+            if st != 0:
+                continue
+            b = (blocks_fn or rule_blocks)(tree, e, v, dcp)
+            out[i, e] = oracle.gp_lnlike(tree.x[sl], tree.y[sl] - f, tree.ye[sl], *hyper(tree, e, v), b)
+    return out

@@ -168,3 +168,71 @@ def test_gp_tree_e1_spec_chain(cases, layout):
     for a, b in zip(*out):
         np.testing.assert_array_equal(a, b)
     assert np.all(np.isfinite(out[0][1])) and out[0][2].sum() > 0   # moves were accepted: the acceptance ran
+
+
+# ------------------------------------------------------------ the rule family
+@pytest.fixture(scope="module")
+def rule_cases(oracle):
+    """case -> (tree, walkers, the double's dist_cp values, the host reference
+    lnlike_e from the double's blocks, the oracle's ln_prob), once"""
+    from lfit_python_amd import batch
+    out = {}
+
+    def get(name):
+        if name not in out:
+            m, walk = gp_trees.rule_case(oracle, name)
+            t = batch.compile_tree(m)
+            dcp = gp_trees.rule_dcp()
+            lnp, _, _ = oracle.lnprob_batch(walk, t)
+            out[name] = (t, walk, dcp, gp_trees.rule_reference(oracle, t, walk, dcp), lnp)
+        return out[name]
+    return get
+
+
+@LAYOUTS
+@pytest.mark.parametrize("name", gp_trees.RULE_CASES)
+def test_gp_rule_edges(oracle, rule_cases, name, layout):
+    """MODEL_SPEC 10.3's cache rule just either side of base / 2.2, above the
+    base, with two parameters tripped, and the device's own dist_cp of every
+    tripped walker, through lnlike_e: data sit 1e-8 .. 1e-4 either side of
+    every edge the double's dist_cp gives (tests/gp_trees.py), so a dist_cp
+    off by 1e-8 or the wrong side of the rule moves lnlike_e by 100 bars or
+    more (tests/test_gp_trees.py::test_rule_case_is_sound).  rule_e3 goes
+    through 7 walkers a call: 21 pairs, tripped and cached ones in one
+    k_gp_dcp block, the last block partial."""
+    import torch
+    from lfit_python_amd import batch
+    t, walk, dcp, ref, lnp_ref = rule_cases(name)
+    ev = batch.LnProbEvaluator(t)
+    assert (_layout_of(ev) != 0) == (layout == 1)
+    k = gp_trees.RULE_CALL_W[name]
+    lnp, lle = np.empty(len(walk)), np.empty((len(walk), t.E))
+    for i in range(0, len(walk), k):
+        l = torch.empty((len(walk[i:i + k]), t.E), dtype=torch.float64, device="cuda")
+        lnp[i:i + k] = ev(torch.as_tensor(walk[i:i + k], device="cuda"), lnlike_e=l).cpu().numpy()
+        lle[i:i + k] = l.cpu().numpy()
+    fin = np.isfinite(lnp_ref)
+    assert np.array_equal(np.isfinite(lnp), fin) and fin[:-1].all() and np.isneginf(lnp[-1])
+    rel = np.abs(lle[fin] - ref[fin]) / np.maximum(1.0, np.abs(ref[fin]))
+    for rname, r in zip(gp_trees.RULE_ROWS, rel):
+        print("%s layout %d %-10s lnlike_e against the double's blocks: %.2e" % (name, layout, rname, r.max()))
+    assert rel.max() <= GP_BAR, (name, layout, rel)
+    _same(lnp, lnp_ref, LNP_RTOL)
+
+
+def test_gp_rule_predict(oracle, rule_cases):
+    """predict() on a tripped row and on the row just short of tripping: the
+    smoother on the blocks the double's rule gives"""
+    import torch
+    from lfit_python_amd import batch
+    t, walk, dcp, ref, lnp_ref = rule_cases("rule_e1")
+    rows = [gp_trees.RULE_ROWS.index(n) for n in ("trip_rwd", "keep_rwd", "two")]
+    ev = batch.LnProbEvaluator(t)
+    pred = {k: v.cpu().numpy() for k, v in ev.predict(torch.as_tensor(walk[rows], device="cuda")).items()
+            if k in ("flux", "gp_mean", "gp_var", "status")}
+    assert (pred["status"] == 0).all()
+    for j, i in enumerate(rows):
+        st, flux = oracle.flux(gp_trees.eclipse_pars(t, 0, walk[i]), t.x, t.w)
+        assert st == 0 and np.max(np.abs(pred["flux"][j] - flux)) <= 1e-9 * np.max(np.abs(flux))
+        gs.check(pred["gp_mean"][j], pred["gp_var"][j], t.x, t.ye, t.y - pred["flux"][j],
+                 gp_trees.hyper(t, 0, walk[i]), gp_trees.rule_blocks(t, 0, walk[i], dcp), t.x)

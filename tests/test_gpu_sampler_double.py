@@ -283,6 +283,7 @@ def test_every_mutation_is_seen(mutate):
 
 # --------------------------------------------- part 2: the modes against the host chain
 ITERS = 5
+TRIP_SEED0, TRIP_SEED = 41, 41
 OUTSIDE = 1   # the walker that starts outside q's uniform prior in `odd` and `nine`
 #        W     ranks   tree       a    seed        first step   layouts          graph
 CASES = {
@@ -302,6 +303,12 @@ CASES = {
     # units are compiled apart from the rest).
     "wave_parts": (130, (5,), "complex", 1.3, 21, 0, ("pair", "two_kernel"), True),
     "long_parts": (10, (5,), "long", 1.3, 102, 0, ("default",), False),
+    # MODEL_SPEC 10.3's cache rule in the middle of the ensemble: the E = 1 ladder tree of tests/gp_trees.py
+    # with the cache's rwd at 2.2 x the start value and its dist_cp unfilled (the device fills it), so that
+    # walkers below the start rwd trip the rule (k_gp_dcp; in k_pair<GP> wave 0's lanes write G_GP_DCP and
+    # G_GP_OK of the slot wave 7 copies the chosen candidate's record into) and those above it do not.  The
+    # first seed from TRIP_SEED0 at which _check_preconditions' conditions for this case hold.
+    "gp_trip": (12, (1, 3), "gp_trip", 2.5, TRIP_SEED, 0, ("pair", "two_kernel"), True),
 }
 # cases in which an accepted move sits on a draw where the readings part
 PARTED = ("wave_parts", "long_parts")
@@ -334,10 +341,17 @@ def _tree(kind, oracle):
         elif kind == "long":
             nsub = 3
             m = synthetic.config_single(513, flux_fn=_flux_fn, nsub=3)
+        elif kind == "gp_trip":
+            from tests import gp_trees
+            m, _ = gp_trees.rule_case(oracle, "rule_e1")
         else:
             from tests import gp_trees
             m, nsub = gp_trees._tree(oracle, "cuts")
-        _trees[kind] = (m, batch.compile_tree(m, nsub=nsub))
+        t = batch.compile_tree(m, nsub=nsub)
+        if kind == "gp_trip":
+            t.gp_base[:, 2] *= 2.2
+            t.gp_base[:, 3] = np.nan
+        _trees[kind] = (m, t)
     return _trees[kind]
 
 
@@ -481,6 +495,47 @@ def _check_preconditions(name, c, a, seed, step0):
         assert parted > 0, name
 
 
+def _trip_conditions(t, init, c, a, seed, step0):
+    """gp_trip, on the host chain: the proposals replayed from the recorded
+    decisions; a list of what fails (empty: the case stands)"""
+    from tests import gp_trees
+    from tests import wdphases_double as wd
+    base = tuple(t.gp_base[0, :3])
+    ns = c.acc.shape[2]
+
+    def trip(rows):
+        p = np.array([gp_trees.eclipse_pars(t, 0, v) for v in rows])
+        near = [abs(abs(B - v) / v - wd.RULE) <= 1e-6 * wd.RULE for B, col in zip(base, (4, 5, 8)) for v in p[:, col]]
+        return np.array([wd.tripped(base, v[4], v[5], v[8]) for v in p]), any(near)
+    pos = np.array(init)
+    prop = {(True, False): 0, (False, True): 0}     # (the walker's row tripped, its proposal tripped)
+    took = dict(prop)
+    near_any, cand1_pending = False, 0
+    for it in range(ITERS):
+        for half in (0, 1):
+            sl = slice(half * ns, (half + 1) * ns)
+            q, _ = sd.propose(pos, half, a, seed, step0 + it, exact=True)
+            now, _ = trip(pos[sl])
+            new, near = trip(q)
+            near_any = near_any or near
+            acc = c.acc[it, half]
+            for k in range(ns):
+                if (now[k], new[k]) in prop:
+                    prop[(now[k], new[k])] += 1
+                    took[(now[k], new[k])] += int(acc[k])
+            if it or half:
+                prev = c.acc[it, 0] if half == 1 else c.acc[it - 1, 1]
+                cand1_pending += int((prev[sd.stretch_draws(ns, half, a, seed, step0 + it)[1]] & new).sum())
+            pos[sl][acc] = q[acc]
+        if not np.array_equal(pos, c.pos[it]):
+            return ["the replay left the chain at step %d" % it]
+    bad = ["no proposal %s -> %s" % k for k, n in prop.items() if n == 0]
+    bad += ["no accepted proposal %s -> %s" % k for k, n in took.items() if n == 0]
+    bad += ["no pending candidate-1 pair"] * (cand1_pending == 0)
+    bad += ["a proposal within 1e-6 of the rule's threshold"] * bool(near_any)
+    return bad
+
+
 @pytest.mark.parametrize("name,lay,mode", _grid())
 def test_mode_matches_the_host_chain(name, lay, mode, oracle):
     """positions, ln_prob and acceptance counters of one mode, bit for bit"""
@@ -494,6 +549,8 @@ def test_mode_matches_the_host_chain(name, lay, mode, oracle):
     ref_lay = "two_kernel" if (R and n * t.E < 2) else lay
     t, init, lnp0, c = _reference(name, ref_lay, oracle)
     _check_preconditions(name, c, a, seed, step0)
+    if name == "gp_trip":
+        assert np.isnan(t.gp_base[:, 3]).all() and _trip_conditions(t, init, c, a, seed, step0) == []
     with _Layout(LAYOUT_ID[lay]):
         if R:
             got = _rank_chains(t, init, lnp0, a, seed, step0, R)
