@@ -25,7 +25,8 @@ def build(out=None, march="x86-64-v3", extra=()):
            "-I", HERE, "-I", os.path.join(HERE, "shim"), "-I", os.path.join(ROOT, "lfit_python_amd", "csrc"),
            "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp"),
            os.path.join(HERE, "lfg_cpu_physpar.cpp"), os.path.join(HERE, "lfg_cpu_wd.cpp"),
-           os.path.join(HERE, "lfg_cpu_chain.cpp"), os.path.join(HERE, "lfg_cpu_limbdark.cpp")]
+           os.path.join(HERE, "lfg_cpu_chain.cpp"), os.path.join(HERE, "lfg_cpu_limbdark.cpp"),
+           os.path.join(HERE, "lfg_cpu_corner.cpp")]
     subprocess.run(cmd, check=True)
     return out
 
@@ -254,6 +255,49 @@ class CpuPort:
                None if win is None else win.ctypes.data, out.ctypes.data, C)
         if rc != 0:
             raise ValueError("lfg_cpu_chain_clip: code %d" % rc)
+        return out
+
+    def corner_hist(self, buf, steps, W, row_len, step_ld, walker_ld, cols, ranges, nb, offset=0):
+        """lfg_cpu_corner_hist on the view (include/lfg_corner.h) of the flat
+        float64 array `buf` that starts at element `offset`: a dict of h1
+        [K, nb], h2 [P, nb, nb] (int64) and flag [K]."""
+        buf = np.ascontiguousarray(buf, dtype=np.float64).reshape(-1)
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        K, nb = int(cols.size), int(nb)
+        rng = np.ascontiguousarray(ranges, dtype=np.float64).reshape(-1, 2)
+        assert rng.shape[0] == K
+        if steps > 0 and W > 0 and K and 0 <= cols.min() and cols.max() < row_len:
+            assert offset + (steps - 1) * step_ld + (W - 1) * walker_ld + cols.max() < buf.size
+        P = max(K * (K - 1) // 2, 0)
+        m = max(nb, 1)   # (the outputs of a refused nb only have to exist)
+        out = {"h1": np.full((K, m), -1, np.int64), "h2": np.full((P, m, m), -1, np.int64),
+               "flag": np.full(K, -1, np.int32)}
+        f = self.lib.lfg_cpu_corner_hist
+        f.restype = ctypes.c_int
+        vp, i64, ci = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+        f.argtypes = [vp, i64, i64, ci, i64, i64, vp, ci, vp, ci, vp, vp, vp]
+        rc = f(ctypes.c_void_p(buf.ctypes.data + 8 * int(offset)), int(steps), int(W), int(row_len), int(step_ld),
+               int(walker_ld), cols.ctypes.data, K, rng.ctypes.data, nb, out["h1"].ctypes.data,
+               out["h2"].ctypes.data if K > 1 else None, out["flag"].ctypes.data)
+        if rc != 0:
+            raise ValueError("lfg_cpu_corner_hist: code %d" % rc)
+        return out
+
+    def corner_levels(self, h2, fracs):
+        """lfg_cpu_corner_levels: level [P, nl] (int64) of h2 [P, nb, nb]"""
+        h2 = np.ascontiguousarray(h2, dtype=np.int64)
+        P, nb = h2.shape[0], h2.shape[1]
+        fr = np.ascontiguousarray(fracs, dtype=np.float64).reshape(-1)
+        out = np.full((P, fr.size), -1, np.int64)
+        f = self.lib.lfg_cpu_corner_levels
+        f.restype = ctypes.c_int
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        f.argtypes = [vp, ci, ci, vp, ci, vp]
+        keep = np.zeros(1, np.int64)   # (a valid pointer for P = 0)
+        rc = f(h2.ctypes.data if h2.size else keep.ctypes.data, P, nb, fr.ctypes.data, fr.size,
+               out.ctypes.data if out.size else keep.ctypes.data)
+        if rc != 0:
+            raise ValueError("lfg_cpu_corner_levels: code %d" % rc)
         return out
 
     def lnprob(self, walkers, tree, nthreads=0):

@@ -15,6 +15,7 @@
 #include "lfg_wd.h"
 #include "lfg_chain.h"
 #include "lfg_limbdark.h"
+#include "lfg_corner.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -73,6 +74,16 @@ int lfg_cpu_chain_clip(const long long* n, const double* m2, const double* med,
 int lfg_cpu_limbdark(const double* logg, const double* teff, size_t ld, int n,
                      const lfg_ld_tables* tab, double* out, int* status,
                      int nthreads);
+
+/* lfg_corner_hist's and lfg_corner_levels' twins (include/lfg_corner.h;
+ * MODEL_SPEC 16): the same arguments on host pointers, range included, no
+ * scratch */
+int lfg_cpu_corner_hist(const double* base, long long steps, long long W,
+                        int row_len, long long step_ld, long long walker_ld,
+                        const int* cols, int K, const double* range, int nb,
+                        long long* h1, long long* h2, int* flag);
+int lfg_cpu_corner_levels(const long long* h2, int P, int nb,
+                          const double* fracs, int nl, long long* level);
 
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */

@@ -30,7 +30,8 @@ SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "
            os.path.join(_HERE, "csrc", "lfg_physpar.hip"),  # physical parameters from chain rows (lfg_physpar.h)
            os.path.join(_HERE, "csrc", "lfg_wd.hip"),  # the white-dwarf atmosphere fit (lfg_wd.h)
            os.path.join(_HERE, "csrc", "lfg_chain.hip"),  # a chain's summary (lfg_chain.h)
-           os.path.join(_HERE, "csrc", "lfg_limbdark.hip")]  # limb-darkening coefficients (lfg_limbdark.h)
+           os.path.join(_HERE, "csrc", "lfg_limbdark.hip"),  # limb-darkening coefficients (lfg_limbdark.h)
+           os.path.join(_HERE, "csrc", "lfg_corner.hip")]  # a corner plot's histograms and levels (lfg_corner.h)
 # k_pair's fold and LONG instantiations: the kernels header, compiled a second
 # time without machine LICM (the reason: lfg_kernels.hpp, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -41,7 +42,8 @@ HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join
                                                    os.path.join(REPO, "include", "lfg_physpar.h"),
                                                    os.path.join(REPO, "include", "lfg_wd.h"),
                                                    os.path.join(REPO, "include", "lfg_chain.h"),
-                                                   os.path.join(REPO, "include", "lfg_limbdark.h")]
+                                                   os.path.join(REPO, "include", "lfg_limbdark.h"),
+                                                   os.path.join(REPO, "include", "lfg_corner.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 
@@ -151,6 +153,11 @@ class LfgLdTables(ctypes.Structure):
     """ctypes mirror of struct lfg_ld_tables (include/lfg_limbdark.h)."""
     _fields_ = [("tx", ctypes.c_void_p), ("ty", ctypes.c_void_p), ("nx", ctypes.c_int), ("ny", ctypes.c_int),
                 ("c", ctypes.c_void_p)]
+
+# include/lfg_corner.h: a corner plot's data, a set of its own too
+EXPORTS_CORNER = ("lfg_corner_workspace_size", "lfg_corner_tile_rows", "lfg_corner_pair_tile", "lfg_corner_hist",
+                  "lfg_corner_levels")
+CORNER_MAX_K, CORNER_MAX_BINS, CORNER_MAX_LEVELS = 64, 64, 8  # LFG_CORNER_* (include/lfg_corner.h)
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -363,6 +370,17 @@ def lib():
         L.lfg_limbdark.argtypes = [vp, vp, sz, ip, ctypes.POINTER(LfgLdTables), vp, vp, vp]
         L.lfg_limbdark_lanes.restype = ip
         L.lfg_limbdark_lanes.argtypes = []
+        L.lfg_corner_workspace_size.restype = sz
+        L.lfg_corner_workspace_size.argtypes = [i64, i64, ip, ip]
+        L.lfg_corner_tile_rows.restype = ip
+        L.lfg_corner_tile_rows.argtypes = []
+        L.lfg_corner_pair_tile.restype = ip
+        L.lfg_corner_pair_tile.argtypes = [ip]
+        L.lfg_corner_hist.restype = ip
+        L.lfg_corner_hist.argtypes = [vp, i64, i64, ip, i64, i64, ctypes.POINTER(ip), ip, vp, ip, vp, vp, vp, vp, sz,
+                                      vp]
+        L.lfg_corner_levels.restype = ip
+        L.lfg_corner_levels.argtypes = [vp, ip, ip, ctypes.POINTER(f64), ip, vp, vp]
         if hasattr(L, "lfg_set_layout"):  # (older experiment builds lack it)
             L.lfg_set_layout.restype = ip
             L.lfg_set_layout.argtypes = [ip]

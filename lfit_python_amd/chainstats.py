@@ -232,7 +232,7 @@ def model_report(model, heading):
 
 
 def fit_summary(chain, names, input_file=None, nskip=0, thin=1, out_dir=".", lnprob=None, walker_major=False,
-                log=print):
+                log=print, corners=False, corner_plots=True):
     """The numbers of the reference's fit_summary.  Writes modparams.csv (mean,
     84th and 16th percentile of every chain parameter, in header order) into
     out_dir.  With input_file the model is rebuilt and evaluated at its start
@@ -245,10 +245,19 @@ def fit_summary(chain, names, input_file=None, nskip=0, thin=1, out_dir=".", lnp
 
     One deliberate difference: thin thins, [nskip::thin], as flatchain does.
     In the reference thin never reaches the summarised frame; at the default
-    thin = 1 the two agree.  Plots and e-mail are out of scope.
+    thin = 1 the two agree.  The model plots and e-mail are out of scope.
+
+    corners=True (with input_file) adds the reference's corner plots, from
+    counts made on the device (corner.eclipse_corners): per eclipse
+    <out_dir>/Final_figs/<lightcurve stem>_corners.npz and, where matplotlib
+    imports, _corners.png (corner_plots=False: the counts alone; matplotlib
+    needs seconds per eclipse for a 20-column triangle).  The reference draws
+    them by default; here they are opt-in, so that existing callers see no
+    change.
 
     -> dict: modparams (the path), result (the DataFrame), stats (ChainStats),
-    initial_report, final_report, lnprob_mean, lnprob_std."""
+    initial_report, final_report, lnprob_mean, lnprob_std, and with corners
+    the list of files written."""
     names = list(names)
     s = stats(chain, cols=len(names), quantiles=(0.16, 0.84), nskip=nskip, thin=thin, walker_major=walker_major)
     path, result = write_modparams(names, s.mean, s.quant[:, 1], s.quant[:, 0], out_dir)
@@ -262,6 +271,11 @@ def fit_summary(chain, names, input_file=None, nskip=0, thin=1, out_dir=".", lnp
         model.dynasty_par_dict = {k: float(m) for k, m in zip(names, s.mean)}
         out["final_report"] = model_report(model, "MCMC result")
         log(out["final_report"])
+        if corners:
+            from . import corner
+            out["corners"] = corner.eclipse_corners(chain, names, model, os.path.join(out_dir, "Final_figs"),
+                                                    nskip=nskip, thin=thin, walker_major=walker_major,
+                                                    plot=corner_plots, log=log)
     if lnprob is not None:
         import torch
         lp = torch.as_tensor(lnprob, dtype=torch.float64)

@@ -1,7 +1,11 @@
 """The summary of a finished chain file: modparams.csv and the before/after
 report of the reference's fit_summary (chainstats.fit_summary).
 
-    python -m lfit_python_amd.fit_summary CHAIN INPUT [--nskip N] [--thin K] [--dir D]
+    python -m lfit_python_amd.fit_summary CHAIN INPUT [--nskip N] [--thin K] [--dir D] [--corners]
+
+--corners adds, per eclipse, the corner plot's counts made on the device
+(D/Final_figs/<lightcurve>_corners.npz, and .png where matplotlib imports).
+The reference draws corner plots by default; here they are opt-in.
 """
 import argparse
 import sys
@@ -16,15 +20,18 @@ def main(argv=None):
     ap.add_argument("--nskip", type=int, default=0)
     ap.add_argument("--thin", type=int, default=1)
     ap.add_argument("--dir", default=".", help="where modparams.csv goes")
+    ap.add_argument("--corners", action="store_true", help="write the corner plots' data (and figures) per eclipse")
     args = ap.parse_args(argv)
     with open(args.chain) as fh:
         names = fh.readline().split()[1:-1]   # 'walker_no <names> ln_prob'
     chain = sampler.read_chain(args.chain)    # [W][steps][npars + 1]
     out = chainstats.fit_summary(chain, names, input_file=args.input, nskip=args.nskip, thin=args.thin,
-                                 out_dir=args.dir, walker_major=True)
+                                 out_dir=args.dir, walker_major=True, corners=args.corners)
     print("Result of the chain:")
     print(out["result"].to_string())
     print("Wrote {}".format(out["modparams"]))
+    for path in out.get("corners", ()):
+        print("Wrote {}".format(path))
     return 0
 
 

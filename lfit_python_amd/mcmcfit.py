@@ -20,8 +20,9 @@ level about the best cold walker, reset, and the cold level's chain written
 to chain_prod.txt with its log posterior as ln_prob.  One process only.
 With --summary (run(..., summary=True)) rank 0 then summarises the production
 chain where it lies on the device (chainstats.fit_summary) and writes
-modparams.csv next to the chain file.  The plots and the e-mail are out of
-scope.
+modparams.csv next to the chain file; with --corners as well it writes, per
+eclipse, the corner plot's counts (corner.eclipse_corners) under Final_figs/
+there.  The model plots and the e-mail are out of scope.
 """
 import argparse
 import os
@@ -76,7 +77,7 @@ def degrees_of_freedom(model):
 
 
 def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt", chunk=None, log=print,
-        summary=False):
+        summary=False, corners=False):
     import torch
     dist = torch.distributed
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -150,7 +151,8 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
         first = False
         done += k
     acc = float(np.mean(S.acceptance_fraction))
-    summ = _summarise(S.chain_dev, S.lnprob_dev, names, input_file, chain_file, say) if summary and rank == 0 else None
+    summ = (_summarise(S.chain_dev, S.lnprob_dev, names, input_file, chain_file, say, corners)
+            if summary and rank == 0 else None)
     S.close()  # the direct RCCL communicator, before the process group goes
     say("Mean acceptance fraction: {:.3f}".format(acc))
     out = {"status": "ok", "chain_file": chain_file, "acceptance": acc, "nwalkers": nwalkers, "npars": npars,
@@ -160,11 +162,12 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
     return out
 
 
-def _summarise(chain, lnprob, names, input_file, chain_file, say):
+def _summarise(chain, lnprob, names, input_file, chain_file, say, corners=False):
     """the production chain's summary, from the device tensors"""
     from . import chainstats
     return chainstats.fit_summary(chain, names, input_file=input_file,
-                                  out_dir=os.path.dirname(os.path.abspath(chain_file)), lnprob=lnprob, log=say)
+                                  out_dir=os.path.dirname(os.path.abspath(chain_file)), lnprob=lnprob, log=say,
+                                  corners=corners)
 
 
 def _run_pt(rc, tree, names, pars, s1, s2, dev, seed, chain_file, chunk, say):
@@ -208,6 +211,9 @@ def main(argv=None):
     ap.add_argument("--chain", default="chain_prod.txt")
     ap.add_argument("--summary", action="store_true",
                     help="summarise the production chain on the device: modparams.csv next to the chain file")
+    ap.add_argument("--corners", action="store_true",
+                    help="with --summary: per eclipse the corner plot's counts (Final_figs/*_corners.npz, and "
+                         ".png where matplotlib imports), made on the device")
     args = ap.parse_args(argv)
     import torch
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -215,7 +221,7 @@ def main(argv=None):
         torch.cuda.set_device(local)
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local))
     out = run(args.input, quiet=args.quiet, debug=args.debug, seed=args.seed, chain_file=args.chain,
-              summary=args.summary)
+              summary=args.summary, corners=args.corners)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     # the reference leaves through a bare exit() (status 0) for a report-only
