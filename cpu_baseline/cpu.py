@@ -26,7 +26,7 @@ def build(out=None, march="x86-64-v3", extra=()):
            "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp"),
            os.path.join(HERE, "lfg_cpu_physpar.cpp"), os.path.join(HERE, "lfg_cpu_wd.cpp"),
            os.path.join(HERE, "lfg_cpu_chain.cpp"), os.path.join(HERE, "lfg_cpu_limbdark.cpp"),
-           os.path.join(HERE, "lfg_cpu_corner.cpp")]
+           os.path.join(HERE, "lfg_cpu_corner.cpp"), os.path.join(HERE, "lfg_cpu_chaintext.cpp")]
     subprocess.run(cmd, check=True)
     return out
 
@@ -299,6 +299,40 @@ class CpuPort:
         if rc != 0:
             raise ValueError("lfg_cpu_corner_levels: code %d" % rc)
         return out
+
+    def chain_text(self, buf, steps, W, ndim, step_ld, walker_ld, lnp, lnp_step_ld, lnp_walker_ld, walker0=0,
+                   offset=0, lnp_offset=0, nthreads=0):
+        """lfg_cpu_chain_text on the views (include/lfg_chaintext.h) of the
+        flat float64 arrays `buf` and `lnp` that start at elements `offset`
+        and `lnp_offset`: the rows' bytes"""
+        buf = np.ascontiguousarray(buf, dtype=np.float64).reshape(-1)
+        lnp = np.ascontiguousarray(lnp, dtype=np.float64).reshape(-1)
+        steps, W, ndim = int(steps), int(W), int(ndim)
+        vp, i64, ci = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+        b = self.lib.lfg_cpu_chain_text_bound
+        b.restype = i64
+        b.argtypes = [i64, i64, ci, i64]
+        bound = b(steps, W, ndim, int(walker0))
+        if bound < 0:
+            raise ValueError("lfg_cpu_chain_text: refused shape")
+        if steps > 0 and W > 0:
+            assert offset + (steps - 1) * step_ld + (W - 1) * walker_ld + ndim <= buf.size
+            assert lnp_offset + (steps - 1) * lnp_step_ld + (W - 1) * lnp_walker_ld < lnp.size
+            # the bound leaves out '%f' of 2^63 and beyond (at most 317 characters)
+            with np.errstate(invalid="ignore"):
+                big = np.isfinite(lnp) & (np.abs(lnp) >= 2.0 ** 63)
+            bound += 320 * int(big.sum())
+        out = np.empty(max(bound, 1), dtype=np.uint8)
+        nb = np.zeros(2, dtype=np.int64)
+        f = self.lib.lfg_cpu_chain_text
+        f.restype = ci
+        f.argtypes = [vp, i64, i64, ci, i64, i64, vp, i64, i64, i64, vp, ctypes.c_size_t, vp, ci]
+        rc = f(ctypes.c_void_p(buf.ctypes.data + 8 * int(offset)), steps, W, ndim, int(step_ld), int(walker_ld),
+               ctypes.c_void_p(lnp.ctypes.data + 8 * int(lnp_offset)), int(lnp_step_ld), int(lnp_walker_ld),
+               int(walker0), out.ctypes.data, bound, nb.ctypes.data, int(nthreads))
+        if rc != 0:
+            raise ValueError("lfg_cpu_chain_text: code %d" % rc)
+        return out[:int(nb[0])].tobytes()
 
     def lnprob(self, walkers, tree, nthreads=0):
         """lfg_cpu_lnprob through a struct lfg_tree of host arrays"""

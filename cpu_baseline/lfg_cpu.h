@@ -16,6 +16,7 @@
 #include "lfg_chain.h"
 #include "lfg_limbdark.h"
 #include "lfg_corner.h"
+#include "lfg_chaintext.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -84,6 +85,20 @@ int lfg_cpu_corner_hist(const double* base, long long steps, long long W,
                         long long* h1, long long* h2, int* flag);
 int lfg_cpu_corner_levels(const long long* h2, int P, int nb,
                           const double* fracs, int nl, long long* level);
+
+/* lfg_chain_text's twin (include/lfg_chaintext.h; MODEL_SPEC 17): the same
+ * arguments on host pointers, no scratch.  Exact for every double: a finite
+ * |lnp| >= 2^63 goes through snprintf("%f"), so nbytes[1] is always 0 */
+int lfg_cpu_chain_text(const double* base, long long steps, long long W,
+                       int ndim, long long step_ld, long long walker_ld,
+                       const double* lnp, long long lnp_step_ld,
+                       long long lnp_walker_ld, long long walker0,
+                       unsigned char* out, size_t out_bytes, long long* nbytes,
+                       int nthreads);
+/* lfg_chain_text_bound's twin.  The bound leaves out what the device refuses:
+ * a caller adds 320 bytes per finite |lnp| >= 2^63 */
+long long lfg_cpu_chain_text_bound(long long steps, long long W, int ndim,
+                                   long long walker0);
 
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */

@@ -31,7 +31,8 @@ SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "
            os.path.join(_HERE, "csrc", "lfg_wd.hip"),  # the white-dwarf atmosphere fit (lfg_wd.h)
            os.path.join(_HERE, "csrc", "lfg_chain.hip"),  # a chain's summary (lfg_chain.h)
            os.path.join(_HERE, "csrc", "lfg_limbdark.hip"),  # limb-darkening coefficients (lfg_limbdark.h)
-           os.path.join(_HERE, "csrc", "lfg_corner.hip")]  # a corner plot's histograms and levels (lfg_corner.h)
+           os.path.join(_HERE, "csrc", "lfg_corner.hip"),  # a corner plot's histograms and levels (lfg_corner.h)
+           os.path.join(_HERE, "csrc", "lfg_chaintext.hip")]  # chain_prod.txt's rows (lfg_chaintext.h)
 # k_pair's fold and LONG instantiations: the kernels header, compiled a second
 # time without machine LICM (the reason: lfg_kernels.hpp, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -43,7 +44,8 @@ HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join
                                                    os.path.join(REPO, "include", "lfg_wd.h"),
                                                    os.path.join(REPO, "include", "lfg_chain.h"),
                                                    os.path.join(REPO, "include", "lfg_limbdark.h"),
-                                                   os.path.join(REPO, "include", "lfg_corner.h")]
+                                                   os.path.join(REPO, "include", "lfg_corner.h"),
+                                                   os.path.join(REPO, "include", "lfg_chaintext.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 
@@ -158,6 +160,11 @@ class LfgLdTables(ctypes.Structure):
 EXPORTS_CORNER = ("lfg_corner_workspace_size", "lfg_corner_tile_rows", "lfg_corner_pair_tile", "lfg_corner_hist",
                   "lfg_corner_levels")
 CORNER_MAX_K, CORNER_MAX_BINS, CORNER_MAX_LEVELS = 64, 64, 8  # LFG_CORNER_* (include/lfg_corner.h)
+
+# include/lfg_chaintext.h: chain_prod.txt's rows, a set of its own too
+EXPORTS_CHAINTEXT = ("lfg_chain_text_bound", "lfg_chain_text_workspace_size", "lfg_chain_text_tile_rows",
+                     "lfg_chain_text")
+CHAIN_TEXT_MAX_NDIM = 1023  # LFG_CHAIN_TEXT_MAX_NDIM (include/lfg_chaintext.h)
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -381,6 +388,14 @@ def lib():
                                       vp]
         L.lfg_corner_levels.restype = ip
         L.lfg_corner_levels.argtypes = [vp, ip, ip, ctypes.POINTER(f64), ip, vp, vp]
+        L.lfg_chain_text_bound.restype = i64
+        L.lfg_chain_text_bound.argtypes = [i64, i64, ip, i64]
+        L.lfg_chain_text_workspace_size.restype = sz
+        L.lfg_chain_text_workspace_size.argtypes = [i64, i64, ip]
+        L.lfg_chain_text_tile_rows.restype = ip
+        L.lfg_chain_text_tile_rows.argtypes = [ip]
+        L.lfg_chain_text.restype = ip
+        L.lfg_chain_text.argtypes = [vp, i64, i64, ip, i64, i64, vp, i64, i64, i64, vp, sz, vp, vp, sz, vp]
         if hasattr(L, "lfg_set_layout"):  # (older experiment builds lack it)
             L.lfg_set_layout.restype = ip
             L.lfg_set_layout.argtypes = [ip]

@@ -94,7 +94,7 @@ def run_mcmc_save(sampler, startPos, nSteps, rState, file, col_names='', progres
         sampler.run_mcmc(startPos if first else None, k, storechain=True, lnprob0=lnprob0 if first else None)
         if writer:
             ch, lp = sampler.last_run()
-            _sampler.write_chain(file, None, ch.cpu().numpy(), lp.cpu().numpy(), mode="a")
+            _sampler.write_chain(file, None, ch, lp, mode="a")  # formatted where the chunk lies
         first = False
         done += k
     return sampler

@@ -146,8 +146,7 @@ def run(input_file, quiet=False, debug=False, seed=0, chain_file="chain_prod.txt
         S.run_mcmc(None if not first else pos, k, storechain=True, lnprob0=None if not first else prob)
         if rank == 0:
             ch, lp = S.last_run()
-            sampler.write_chain(chain_file, names, ch.cpu().numpy(), lp.cpu().numpy(),
-                                mode="w" if first else "a")
+            sampler.write_chain(chain_file, names, ch, lp, mode="w" if first else "a")
         first = False
         done += k
     acc = float(np.mean(S.acceptance_fraction))

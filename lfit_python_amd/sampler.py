@@ -675,17 +675,16 @@ def initialise_walkers(p, scatter, nwalkers, ln_prob_fn, seed=0, max_rounds=1000
 def write_chain(fname, names, chain, lnprob, mode="w"):
     """chain_prod.txt in the reference's format (mcmcfit.py:317,
     mcmc_utils.py:157-164): header `walker_no <names> ln_prob`, then one row
-    per walker per step: '{k:4d} {repr(x) ...} {lnp:f}'."""
-    chain = np.asarray(chain)
-    lnprob = np.asarray(lnprob)
-    with open(fname, mode) as fh:
+    per walker per step: '{k:4d} {repr(x) ...} {lnp:f}'.  chain [steps, W,
+    ndim] and lnprob [steps, W] are arrays or tensors, on the host or on the
+    device: the rows are formatted in bulk where the chain lies
+    (chaintext.format_rows) and written with one write."""
+    from . import chaintext
+    rows = chaintext.format_rows(chain, lnprob)
+    with open(fname, mode + "b") as fh:
         if mode == "w":
-            fh.write("walker_no " + " ".join(names) + " ln_prob\n")
-        for s in range(chain.shape[0]):
-            rows = ["{0:4d} {1:s} {2:f}\n".format(k, " ".join(map(repr, map(float, chain[s, k]))),
-                                                 float(lnprob[s, k]))
-                    for k in range(chain.shape[1])]
-            fh.write("".join(rows))
+            fh.write(("walker_no " + " ".join(names) + " ln_prob\n").encode())
+        fh.write(rows)
 
 
 def read_chain(fname):
