@@ -26,7 +26,8 @@ def build(out=None, march="x86-64-v3", extra=()):
            "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(HERE, "lfg_cpu.cpp"),
            os.path.join(HERE, "lfg_cpu_physpar.cpp"), os.path.join(HERE, "lfg_cpu_wd.cpp"),
            os.path.join(HERE, "lfg_cpu_chain.cpp"), os.path.join(HERE, "lfg_cpu_limbdark.cpp"),
-           os.path.join(HERE, "lfg_cpu_corner.cpp"), os.path.join(HERE, "lfg_cpu_chaintext.cpp")]
+           os.path.join(HERE, "lfg_cpu_corner.cpp"), os.path.join(HERE, "lfg_cpu_chaintext.cpp"),
+           os.path.join(HERE, "lfg_cpu_chainparse.cpp")]
     subprocess.run(cmd, check=True)
     return out
 

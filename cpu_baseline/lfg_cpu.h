@@ -100,6 +100,19 @@ int lfg_cpu_chain_text(const double* base, long long steps, long long W,
 long long lfg_cpu_chain_text_bound(long long steps, long long W, int ndim,
                                    long long walker0);
 
+/* lfg_chain_parse_count's and lfg_chain_parse's twins (include/lfg_chainparse.h,
+ * MODEL_SPEC.md section 18): the same arguments without the stream, every
+ * pointer a host pointer.  The twin refuses no token (info[3] stays 0): what
+ * the shared rules leave undecided is finished by strtod in the C locale. */
+int lfg_cpu_chain_parse_tile_bytes(void);
+size_t lfg_cpu_chain_parse_workspace_size(long long nbytes);
+int lfg_cpu_chain_parse_count(const unsigned char* text, long long nbytes,
+                              int ncol, long long* info, void* ws,
+                              size_t ws_bytes);
+int lfg_cpu_chain_parse(const unsigned char* text, long long nbytes, int ncol,
+                        double* out, long long out_rows, long long* info,
+                        void* ws, size_t ws_bytes);
+
 /* the batch form bench.py times (the oracle's lfo_lnprob_batch arguments);
  * returns the OpenMP threads used */
 int lfc_lnprob_batch(const double* walkers, int W, int ndim, int E,

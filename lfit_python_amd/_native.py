@@ -32,7 +32,8 @@ SOURCES = [os.path.join(_HERE, "csrc", "lfg.hip"), os.path.join(_HERE, "csrc", "
            os.path.join(_HERE, "csrc", "lfg_chain.hip"),  # a chain's summary (lfg_chain.h)
            os.path.join(_HERE, "csrc", "lfg_limbdark.hip"),  # limb-darkening coefficients (lfg_limbdark.h)
            os.path.join(_HERE, "csrc", "lfg_corner.hip"),  # a corner plot's histograms and levels (lfg_corner.h)
-           os.path.join(_HERE, "csrc", "lfg_chaintext.hip")]  # chain_prod.txt's rows (lfg_chaintext.h)
+           os.path.join(_HERE, "csrc", "lfg_chaintext.hip"),  # chain_prod.txt's rows (lfg_chaintext.h)
+           os.path.join(_HERE, "csrc", "lfg_chainparse.hip")]  # chain_prod.txt's numbers read back (lfg_chainparse.h)
 # k_pair's fold and LONG instantiations: the kernels header, compiled a second
 # time without machine LICM (the reason: lfg_kernels.hpp, lfg_pair_launch_split)
 SPLIT_SOURCE = os.path.join(_HERE, "csrc", "lfg_pair_split.hip")
@@ -45,7 +46,8 @@ HEADERS = sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join
                                                    os.path.join(REPO, "include", "lfg_chain.h"),
                                                    os.path.join(REPO, "include", "lfg_limbdark.h"),
                                                    os.path.join(REPO, "include", "lfg_corner.h"),
-                                                   os.path.join(REPO, "include", "lfg_chaintext.h")]
+                                                   os.path.join(REPO, "include", "lfg_chaintext.h"),
+                                                   os.path.join(REPO, "include", "lfg_chainparse.h")]
 INCLUDE = os.path.join(REPO, "include")
 ARCH = "gfx950"
 
@@ -165,6 +167,11 @@ CORNER_MAX_K, CORNER_MAX_BINS, CORNER_MAX_LEVELS = 64, 64, 8  # LFG_CORNER_* (in
 EXPORTS_CHAINTEXT = ("lfg_chain_text_bound", "lfg_chain_text_workspace_size", "lfg_chain_text_tile_rows",
                      "lfg_chain_text")
 CHAIN_TEXT_MAX_NDIM = 1023  # LFG_CHAIN_TEXT_MAX_NDIM (include/lfg_chaintext.h)
+
+# include/lfg_chainparse.h: chain_prod.txt's numbers read back, a set of its own too
+EXPORTS_CHAINPARSE = ("lfg_chain_parse_tile_bytes", "lfg_chain_parse_workspace_size", "lfg_chain_parse_count",
+                      "lfg_chain_parse")
+CHAIN_PARSE_MAX_TOKEN, CHAIN_PARSE_MAX_NCOL = 64, CHAIN_TEXT_MAX_NDIM + 2  # LFG_CHAIN_PARSE_* (include/lfg_chainparse.h)
 
 
 FLAGS = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
@@ -396,6 +403,14 @@ def lib():
         L.lfg_chain_text_tile_rows.argtypes = [ip]
         L.lfg_chain_text.restype = ip
         L.lfg_chain_text.argtypes = [vp, i64, i64, ip, i64, i64, vp, i64, i64, i64, vp, sz, vp, vp, sz, vp]
+        L.lfg_chain_parse_tile_bytes.restype = ip
+        L.lfg_chain_parse_tile_bytes.argtypes = []
+        L.lfg_chain_parse_workspace_size.restype = sz
+        L.lfg_chain_parse_workspace_size.argtypes = [i64]
+        L.lfg_chain_parse_count.restype = ip
+        L.lfg_chain_parse_count.argtypes = [vp, i64, ip, vp, vp, sz, vp]
+        L.lfg_chain_parse.restype = ip
+        L.lfg_chain_parse.argtypes = [vp, i64, ip, vp, i64, vp, vp, sz, vp]
         if hasattr(L, "lfg_set_layout"):  # (older experiment builds lack it)
             L.lfg_set_layout.restype = ip
             L.lfg_set_layout.argtypes = [ip]

@@ -38,7 +38,10 @@ def main(argv=None):
     if args.flat > 0:
         # a flattened chain: the header's names after its first word label the columns
         # (the reference's readflatchain would read the header line as data; it is left out here)
-        fchain = np.loadtxt(args.file, skiprows=1, ndmin=2)
+        from . import chainparse
+        fchain = chainparse.try_table(args.file, skip_lines=1)   # (None: the earlier reader decides)
+        if fchain is None:
+            fchain = np.loadtxt(args.file, skiprows=1, ndmin=2)
         nobjects = int((args.flat * len(fchain)) / args.thin)
         fchain = fchain[:nobjects]
     else:

@@ -10,7 +10,7 @@ The reference draws corner plots by default; here they are opt-in.
 import argparse
 import sys
 
-from . import chainstats, sampler
+from . import chainparse, chainstats, sampler
 
 
 def main(argv=None):
@@ -24,9 +24,18 @@ def main(argv=None):
     args = ap.parse_args(argv)
     with open(args.chain) as fh:
         names = fh.readline().split()[1:-1]   # 'walker_no <names> ln_prob'
-    chain = sampler.read_chain(args.chain)    # [W][steps][npars + 1]
+    chain, walker_major = None, False
+    if chainparse.device_available():
+        # the file's bytes to the device once, the doubles formed there: [steps][W][npars + 1],
+        # the same logical view as the host reader's [W][steps] under walker_major
+        try:
+            chain = chainparse.read_chain(args.chain, device="cuda")[0]
+        except ValueError:
+            chain = None                      # (bad, ragged or irregular: the host reader decides)
+    if chain is None:
+        chain, walker_major = sampler.read_chain(args.chain), True    # [W][steps][npars + 1]
     out = chainstats.fit_summary(chain, names, input_file=args.input, nskip=args.nskip, thin=args.thin,
-                                 out_dir=args.dir, walker_major=True, corners=args.corners)
+                                 out_dir=args.dir, walker_major=walker_major, corners=args.corners)
     print("Result of the chain:")
     print(out["result"].to_string())
     print("Wrote {}".format(out["modparams"]))

@@ -338,11 +338,18 @@ def update_input(path, linear_medians, out=None, fmt="%.4f"):
     return changed
 
 
-def read_chain_file(path):
+def read_chain_file(path, device=None):
     """chain_wd.txt as lfit_python_amd.wdparams writes it -> (chain
     [steps][W][ncol], names): the header's names without walker_no, ln_prob
-    included, so that a row is the file's row."""
-    from . import sampler
+    included, so that a row is the file's row.  With device= the file is
+    parsed there (chainparse.read_chain) and the chain is a device tensor; a
+    file the parser will not take is read on the host as without it."""
+    from . import chainparse, sampler
+    if device is not None:
+        try:
+            return chainparse.read_chain(path, device=device)
+        except ValueError:
+            pass                              # (bad, ragged or irregular: the host reader decides)
     with open(path) as fh:
         names = fh.readline().split()[1:]
     chain = sampler.read_chain(path)          # [W][steps][ncol]
@@ -369,7 +376,8 @@ def main(argv=None):
 
     tables = load_ld_tables(args.dir)
     if args.chain:
-        chain, names = read_chain_file(args.chain)
+        from . import chainparse
+        chain, names = read_chain_file(args.chain, device="cuda" if chainparse.device_available() else None)
         table, status = from_chain(chain, names, tables, nskip=args.nskip, thin=args.thin)
     else:
         if args.values:

@@ -184,6 +184,14 @@ def readchain_dask(file, **kwargs):
 
 def readflatchain(file):
     """A whitespace-separated table read with no header row (e.g. a
-    flattened chain) as one array (mcmc_utils.py:303-306: pandas, header=None)."""
+    flattened chain) as one array (mcmc_utils.py:303-306: pandas, header=None).
+
+    Parsed in bulk (chainparse.read_table) where that gives what pandas gives:
+    a table of numbers that are not all whole (pandas keeps a table of whole
+    numbers as integers).  Everything else goes through pandas as before."""
+    from . import chainparse
+    t = chainparse.try_table(file)
+    if t is not None and not np.all(np.isfinite(t) & (t == np.floor(np.where(np.isfinite(t), t, 0.0)))):
+        return t
     import pandas as pd
     return np.array(pd.read_csv(file, header=None, sep=r"\s+", float_precision="round_trip"))

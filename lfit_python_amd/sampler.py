@@ -689,7 +689,22 @@ def write_chain(fname, names, chain, lnprob, mode="w"):
 
 def read_chain(fname):
     """Inverse of write_chain -> chain [nwalkers, nsteps, npars + 1] like
-    mcmc_utils.readchain (mcmc_utils.py:252-272); last column is ln_prob."""
+    mcmc_utils.readchain (mcmc_utils.py:252-272); last column is ln_prob.
+
+    The numbers are parsed in bulk (chainparse.read_chain on the host twin:
+    the doubles float() gives).  A file the parser reports as bad, ragged or
+    with irregular walker numbers, a file of one row, and every file when the
+    twin's library is absent, goes the earlier way: np.loadtxt and a gather
+    per walker."""
+    import os
+    if isinstance(fname, (str, os.PathLike)):
+        from . import chainparse
+        try:
+            grid, _ = chainparse.read_chain(fname)        # [steps][W][npars + 1]
+        except ValueError:
+            grid = None
+        if grid is not None and grid.shape[0] * grid.shape[1] > 1:
+            return np.ascontiguousarray(grid.transpose(1, 0, 2))
     data = np.loadtxt(fname, skiprows=1)
     nw = int(data[:, 0].max()) + 1
     ns = data.shape[0] // nw

@@ -338,7 +338,10 @@ def _read_chain_fluxes(cfg, syserr, corrections):
             line = fh.readline()
         keys = line.strip().split()[1:]
     if int(cfg.get("flat", 0)):
-        fchain = np.loadtxt(chain_file, skiprows=1, ndmin=2)
+        from . import chainparse
+        fchain = chainparse.try_table(chain_file, skip_lines=1)   # (None: the earlier reader decides)
+        if fchain is None:
+            fchain = np.loadtxt(chain_file, skiprows=1, ndmin=2)
     else:
         chain = mcmc_utils.readchain(chain_file)
         print("The chain has the {} walkers, {} steps, and {} pars.".format(*chain.shape))
